@@ -37,6 +37,16 @@ GPU call in the parent); under torch.distributed.run it joins the given ranks.
   --mode weak:   an (N*H) x W image, one H-row shard per rank (no gather).
 --workload 4k: 4096 x 4096 RGB instead of 7680 x 4320 (north_star's 4K point).
 value = pixels encoded by all ranks / max-over-ranks wall time of the K steps.
+
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, runs the W warmup steps, times
+the K steps as one region, writes the outputs when --dump-outputs DIR is given (see
+dump_outputs) and prints the result line: value, ms_per_step and the configuration.
+--full adds everything else to the line: 7 more timed regions (value and ms_per_step
+are then the median of the 8, with the spread), the roofline kernel timed apart, the
+in-run memory floors, the extra configurations (BASELINE configs[1] / configs[4],
+the 4K and ragged encodes, the decode and reference-API timings), the CPU baseline,
+and at N > 1 the gather check, the measured link rate and the sharded 16K round trip.
+--no-extras and --no-cpu-baseline trim a --full run.
 """
 import argparse
 import json
@@ -56,7 +66,10 @@ H8K, W8K = 4320, 7680
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec (MI355X_MICROARCH.md)
 XGMI_LINK_GBS = 153.0  # per xGMI link of an MI355X (7 per GPU), the figure given with this build
 ROT_BYTES = 1.2e9          # rotate >= 1.2 GB of inputs: defeats the 256 MiB Infinity Cache
-REGION_REPEATS = 7         # extra timed regions for the ms_per_step spread (p10 / p50 / p90)
+REGION_REPEATS = 7         # --full: extra timed regions for the ms_per_step spread (p10 / p50 / p90)
+DUMP_SEED = 20             # --dump-outputs: the sample's seed and sizes (64 MB in all at the most)
+DUMP_SYMBOLS = 1 << 20
+DUMP_BLOCKS = 1 << 15
 
 
 def parse():
@@ -90,6 +103,13 @@ def parse():
                          "instead of the slot layout (the fused kernel writes the symbols, one closing scan)")
     ap.add_argument("--knob", action="append", default=[], metavar="NAME=VALUE",
                     help="A/B: set a library knob (hiccup_amd._lib.KNOBS; every knob is bit-exact)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: the repeated timed regions (value = their median), the "
+                         "roofline kernel timed apart, the in-run memory floors, the extra configurations, the "
+                         "CPU baseline, at N > 1 the gather check, the link rate and the sharded 16K round trip")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step's encode left on the device as "
+                         "DIR/<name>.npy (float32 / float64; long arrays as a fixed seeded sample)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-budget-s", type=float, default=25.0)
     ap.add_argument("--no-extras", action="store_true",
@@ -843,6 +863,52 @@ def extra_16k_roundtrip_sharded(rank, world, backend, steps=4):
             "psnr_db_vs_input": round(10 * np.log10(255.0 ** 2 / mse), 3), "timed_roundtrips": steps}
 
 
+def dump_outputs(path, e, prefix="", share=1):
+    """--dump-outputs: what an encode left in pipeline.Encoder `e`, the arrays a caller
+    of the timed path reads, as path/<prefix><name>.npy:
+      counts                    the three channels' symbol counts (float64);
+      dc_<ch>                   every block's DC difference (float32, exact);
+      sym_len_<ch>, sym_val_<ch>  the channel's symbol stream (float32); the slot layout's
+                                through hic_rle_slots_compact, launched here after the timing;
+      index_<ch>                slot layout: the record index the close wrote (float64);
+      coef_<ch>                 coefficient chain: the zig-zag blocks (float32).
+    A stream longer than DUMP_SYMBOLS symbols, or a plane of more than DUMP_BLOCKS
+    blocks, is written as a sample at sorted indices drawn from a generator seeded
+    with DUMP_SEED (the indices depend only on the seed and the array's length):
+    28 MB in all at 8K in the slot layout, 53 MB for the coefficient chain.
+    share: ranks writing into the same directory."""
+    from hiccup_amd import pipeline
+    os.makedirs(path, exist_ok=True)
+    e.compact()
+    torch.cuda.synchronize()
+    gen = torch.Generator()
+
+    def save(name, t, dtype=np.float32):
+        np.save(os.path.join(path, prefix + name + ".npy"), t.cpu().numpy().astype(dtype))
+
+    def sample(t, n, limit):
+        """t[:n], or its rows at min(n, limit) seeded indices when n > limit."""
+        limit = max(1, limit // share)
+        if n <= limit:
+            return t[:n]
+        gen.manual_seed(DUMP_SEED)  # a stream's lengths and values at the same indices
+        idx = torch.randint(0, n, (limit,), generator=gen).sort().values
+        return t[:n].index_select(0, idx.to(t.device))
+
+    counts = e.counts.cpu().tolist()
+    save("counts", e.counts, np.float64)
+    for i, k in enumerate(pipeline.CHANNELS):
+        c = int(counts[i])
+        pipeline.check_count(c, k)
+        save("dc_" + k, e.dc[k])
+        save("sym_len_" + k, sample(e.sym_len[k], c, DUMP_SYMBOLS))
+        save("sym_val_" + k, sample(e.sym_val[k], c, DUMP_SYMBOLS))
+        if e.slots:
+            save("index_" + k, e.sidx[k].view(-1, 4), np.float64)
+        else:
+            save("coef_" + k, sample(e.coef[k], e.coef[k].shape[0], DUMP_BLOCKS))
+
+
 def load_pmc_traffic(fused, slots=False):
     """HBM bytes per launch of the roofline kernel from the committed rocprofv3 PMC
     summary (profiles/pmc_encode_slots.json for the slot-layout kernel,
@@ -962,7 +1028,7 @@ def main():
     fused = enc0.fused
 
     timed_events = []
-    event_pool = [device.KernelEvents() for _ in range((args.steps + 3) // 4)]
+    event_pool = [device.KernelEvents() for _ in range((args.steps + 3) // 4)] if args.full else []
     gather_ev = []  # (start, stop) torch events around each timed step's gather
 
     # consecutive images alternate over the streams (4 rotating encoders: an
@@ -1015,9 +1081,9 @@ def main():
         e = encs[i % len(encs)]
         x = inputs[i % nin]
         ev = None
-        # HIP events carrying the DCT kernel's own begin/end timestamps, on every 4th
-        # timed step (a timestamped dispatch costs the stream a few us)
-        if record and (i - args.warmup) % 4 == 0:
+        # --full: HIP events carrying the DCT kernel's own begin/end timestamps, on every
+        # 4th timed step (a timestamped dispatch costs the stream a few us)
+        if args.full and record and (i - args.warmup) % 4 == 0:
             ev = event_pool[len(timed_events)]
             timed_events.append(ev)
         if gather:
@@ -1055,11 +1121,30 @@ def main():
         return float(t.item())
 
     elapsed = max_over_ranks(elapsed)
-    # the same K-step region (same brackets) repeated: `value` is the median region
-    # (a ~2 ms region moves with box clocks and queue timing), the first
-    # region is reported beside it
+    # in stream-gather mode the streams live on the gathering ranks
+    stream_gather = gather and args.gather_kind == "stream"
+
+    def holder(e):
+        """The pipeline.Encoder holding the stream of encs[j]'s last image on this rank
+        (None: a stream gather took it to another rank)."""
+        if world == 1:
+            return e
+        return e.whole if stream_gather else e.enc
+
+    if args.dump_outputs:
+        # the last timed step's encode: one rank holds it after a stream gather, else
+        # every rank writes its own (its shard's stream, names prefixed with its rank)
+        h = holder(encs[(args.warmup + args.steps - 1) % len(encs)])
+        if h is not None:
+            if world == 1 or stream_gather:
+                dump_outputs(args.dump_outputs, h)
+            else:
+                dump_outputs(args.dump_outputs, h, "rank%d_" % rank, world)
+    # --full: the same K-step region (same brackets) repeated: `value` is then the
+    # median region (VERDICT r4: a ~2 ms region moves with box clocks and queue
+    # timing), the first region is reported beside it
     region_ms = [elapsed / args.steps * 1e3]
-    for rep in range(REGION_REPEATS):
+    for rep in range(REGION_REPEATS if args.full else 0):
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
@@ -1074,15 +1159,12 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
         region_ms.append(max_over_ranks(time.perf_counter() - t1) / args.steps * 1e3)
-    # every step's symbol counts are valid (a failed step would report a negative count);
-    # in stream-gather mode the streams live on the gathering ranks
-    stream_gather = gather and args.gather_kind == "stream"
 
-    # N > 1 stream gather: one more group of N copies of one full image (every rank
-    # makes the same image, encodes its row shard); each gathering rank's received
+    # --full, N > 1 stream gather: one more group of N copies of one full image (every
+    # rank makes the same image, encodes its row shard); each gathering rank's received
     # whole-image streams must equal a single-GPU Encoder's of that image, bit for bit
     verify = None
-    if stream_gather and world > 1:
+    if args.full and stream_gather and world > 1:
         gv = torch.Generator(device="cuda")
         gv.manual_seed(99)
         full = torch.randint(0, 256, (H, W0, 3), dtype=torch.uint8, device="cuda", generator=gv)
@@ -1113,12 +1195,9 @@ def main():
         del full, xs, ref
 
     def counts_of(e):
-        if world == 1:
-            return e.counts
-        if stream_gather:
-            return e.whole.counts if e.whole is not None else None
-        return e.enc.counts
+        return holder(e).counts if holder(e) is not None else None
 
+    # every step's symbol counts are valid (a failed step would report a negative count)
     for e in encs:
         counts = counts_of(e)
         if counts is None:
@@ -1151,48 +1230,49 @@ def main():
                        "per_link_GBps_assumed_peak": XGMI_LINK_GBS,
                        "link_bound_us_per_image": round(img_bytes / world / (XGMI_LINK_GBS * 1e3) / world, 2)}
 
-    # ---- roofline kernel: the DCT+quantize+zig-zag pass (one launch for the three
-    # planes).  hic_dct_quant_rle_u8_batch hands the two HIP events to
-    # hipExtLaunchKernelGGL: they hold that dispatch's begin / end timestamps.
-    dct_us = float(np.mean([ev.elapsed_ms() for ev in timed_events])) * 1e3
-    roof_note = "timed region (every 4th step)"
-    dct_us_overlapped = None
-    if len(streams) > 1 or gather:
-        # with images overlapped on several streams (or a gather in the step) the DCT
-        # shares the chip with other kernels, so its launch duration is no longer its
-        # own: the roofline kernel is timed apart, on the same encoders and inputs,
-        # one stream, right after the timed region
-        dct_us_overlapped = dct_us
-        # as in the timed region: back-to-back steps, the DCT timestamped on every
-        # 4th (8 untimed steps first: the launches right after the overlapped region
-        # run 5-15 % slow in the kernel trace, profiles/r01/bench_s2_kernel_trace_v9)
-        iso = [device.KernelEvents() for _ in range(16)]
-        for j in range(24):
-            ev = iso[j - 8] if j >= 8 else None
-            encs[j % len(encs)].encode(inputs[j % nin], dct_events=ev)
-        torch.cuda.synchronize()
-        dct_us = float(np.median([ev.elapsed_ms() for ev in iso])) * 1e3
-        timed_events = iso
-        roof_note = ("median of 16 single-stream encodes (each timestamped, after 8 untimed) right after the timed "
-                     "region; the timed region overlaps images on %d stream(s)%s"
-                     % (len(streams), " and grouped gathers" if gather else ""))
-    # algorithmic bytes of the timed launch: the two-kernel chain's DCT reads 1 B and
-    # writes 2 B per plane pixel; the fused kernel reads the RGB (3 B per image
-    # pixel) and writes the same coefficients -- or, in the slot layout, the symbols
-    # it emits (1 B length + 2 B value each) and the DC differences (4 B per block)
     slots = world == 1 and enc0.slots
-    nsym_slots = slot_symbols(enc0) if slots else None
-    if slots:
-        roof_bytes = px_per_step_rank * 3 + 3 * nsym_slots + 4 * (dct_px // 64)
-    else:
-        roof_bytes = dct_px * 2 + (px_per_step_rank * 3 if fused else dct_px)
-    achieved = roof_bytes / (dct_us * 1e-6) / 1e9
+    if args.full:
+        # ---- roofline kernel: the DCT+quantize+zig-zag pass (one launch for the three
+        # planes).  hic_dct_quant_rle_u8_batch hands the two HIP events to
+        # hipExtLaunchKernelGGL: they hold that dispatch's begin / end timestamps.
+        dct_us = float(np.mean([ev.elapsed_ms() for ev in timed_events])) * 1e3
+        roof_note = "timed region (every 4th step)"
+        dct_us_overlapped = None
+        if len(streams) > 1 or gather:
+            # with images overlapped on several streams (or a gather in the step) the DCT
+            # shares the chip with other kernels, so its launch duration is no longer its
+            # own: the roofline kernel is timed apart, on the same encoders and inputs,
+            # one stream, right after the timed region
+            dct_us_overlapped = dct_us
+            # as in the timed region: back-to-back steps, the DCT timestamped on every
+            # 4th (8 untimed steps first: the launches right after the overlapped region
+            # run 5-15 % slow in the kernel trace, profiles/r01/bench_s2_kernel_trace_v9)
+            iso = [device.KernelEvents() for _ in range(16)]
+            for j in range(24):
+                ev = iso[j - 8] if j >= 8 else None
+                encs[j % len(encs)].encode(inputs[j % nin], dct_events=ev)
+            torch.cuda.synchronize()
+            dct_us = float(np.median([ev.elapsed_ms() for ev in iso])) * 1e3
+            timed_events = iso
+            roof_note = ("median of 16 single-stream encodes (each timestamped, after 8 untimed) right after the "
+                         "timed region; the timed region overlaps images on %d stream(s)%s"
+                         % (len(streams), " and grouped gathers" if gather else ""))
+        # algorithmic bytes of the timed launch: the two-kernel chain's DCT reads 1 B and
+        # writes 2 B per plane pixel; the fused kernel reads the RGB (3 B per image
+        # pixel) and writes the same coefficients -- or, in the slot layout, the symbols
+        # it emits (1 B length + 2 B value each) and the DC differences (4 B per block)
+        nsym_slots = slot_symbols(enc0) if slots else None
+        if slots:
+            roof_bytes = px_per_step_rank * 3 + 3 * nsym_slots + 4 * (dct_px // 64)
+        else:
+            roof_bytes = dct_px * 2 + (px_per_step_rank * 3 if fused else dct_px)
+        achieved = roof_bytes / (dct_us * 1e-6) / 1e9
 
-    # context for the gathered strong-scaling line: the same steps with the stream
-    # left distributed (no gather), timed the same way -- the sharded encode itself
-    # scales; the gathers are bound by the xGMI links
+    # --full: context for the gathered strong-scaling line: the same steps with the
+    # stream left distributed (no gather), timed the same way -- the sharded encode
+    # itself scales; the gathers are bound by the xGMI links
     no_gather = None
-    if gather and not stream_gather:
+    if args.full and gather and not stream_gather:
         dist.barrier()
         torch.cuda.synchronize()
         t1 = time.perf_counter()
@@ -1218,10 +1298,10 @@ def main():
                     if gather else None)
     extra_sharded = None
     link_gbs = None
-    if world > 1 and args.dist_backend == "nccl" and not args.same_device:
+    if args.full and world > 1 and args.dist_backend == "nccl" and not args.same_device:
         # the per-link rate the gather model uses, measured here (not assumed)
         link_gbs = measure_link(rank, world)
-    if world > 1 and not args.no_extras:
+    if args.full and world > 1 and not args.no_extras:
         # free the 8K run's buffers first (every rank holds ~1.2 GB of inputs)
         del encs, inputs, enc0
         torch.cuda.empty_cache()
@@ -1229,12 +1309,11 @@ def main():
 
     if rank == 0:
         total_px = px_per_step_rank * world * args.steps
-        # value: the median of the 8 timed regions (each K steps between barriers and
-        # synchronisations); the first region's rate beside it
+        # value: the timed region's rate (K steps between barriers and synchronisations);
+        # --full: the median of the 8 timed regions, the first region's rate beside it
         med_ms = float(np.median(region_ms))
         value = total_px / (med_ms * args.steps * 1e-3) / 1e6
         value_first = total_px / elapsed / 1e6
-        pmc = load_pmc_traffic(fused, slots)
         cfg_idx = 2 if world == 1 else 3
         wl = ("%dx%d RGB -> YCrCb 4:2:0 full encode: colour+pyrDown, 8x8 DCT+quantize+zig-zag (3 planes), "
               "DC DPCM + AC RLE (3 planes)" % (W0, H0))
@@ -1258,13 +1337,9 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": round(med_ms, 4),
-            "value_first_region": round(value_first, 2),
-            "ms_per_step_first_region": round(elapsed / args.steps * 1e3, 4),
-            "value_is": "median over the %d timed regions of K steps" % len(region_ms),
-            "ms_per_step_p10": round(float(np.percentile(region_ms, 10)), 4),
-            "ms_per_step_p50": round(float(np.percentile(region_ms, 50)), 4),
-            "ms_per_step_p90": round(float(np.percentile(region_ms, 90)), 4),
-            "ms_per_step_regions": [round(v, 4) for v in region_ms],
+            "value_is": ("median over the %d timed regions of K steps" % len(region_ms) if args.full else
+                         "the timed region of K steps (--full: the median over %d such regions)"
+                         % (1 + REGION_REPEATS)),
             "higher_is_better": True,
             "scaling": "strong" if strong else "weak",
             "vs_baseline": None,
@@ -1293,7 +1368,18 @@ def main():
                                                                               else ""),
                 "parallelism": "dp%d tile-shard" % world,
             },
-            "roofline": {
+        }
+        if args.full:
+            pmc = load_pmc_traffic(fused, slots)
+            out.update({
+                "value_first_region": round(value_first, 2),
+                "ms_per_step_first_region": round(elapsed / args.steps * 1e3, 4),
+                "ms_per_step_p10": round(float(np.percentile(region_ms, 10)), 4),
+                "ms_per_step_p50": round(float(np.percentile(region_ms, 50)), 4),
+                "ms_per_step_p90": round(float(np.percentile(region_ms, 90)), 4),
+                "ms_per_step_regions": [round(v, 4) for v in region_ms],
+            })
+            out["roofline"] = {
                 "bound": "hbm",
                 "kernel": ("k_encode420<15,slots> (RGB -> YCrCb + 4:2:0 pyrDown + AAN DCT + quantize + zig-zag + the "
                            "AC symbols and DC differences of every RLE record, slot layout, in one launch; algorithmic "
@@ -1316,47 +1402,46 @@ def main():
                 "avg_launch_us": round(dct_us, 2),
                 "timed_over": roof_note,
                 "avg_launch_us_overlapped": None if dct_us_overlapped is None else round(dct_us_overlapped, 2),
-            },
-        }
-        if world == 1:
-            floors = measure_floors(slots=slots)
-            out["memory_floors"] = floors
-            out["roofline"]["device_copy_gbs"] = floors["device_copy_gbs"]
-            out["roofline"]["frac_of_device_copy"] = round(achieved / floors["device_copy_gbs"], 4)
-            if fused and args.workload == "8k":
-                # the kernel's own byte pattern without its arithmetic, measured in this run
-                fl = floors["encode420_pattern"]["median_launch_us"]
-                out["roofline"]["memory_floor_us"] = fl
-                out["roofline"]["frac_of_memory_floor"] = round(fl / dct_us, 4)
-                out["roofline"]["memory_floor_source"] = ("memory_floors.encode420_pattern (%s, this run)" %
-                                                          ("hic_probe_encode420_slots" if slots else
-                                                           "hic_probe_encode420"))
-            # the headline normalised by this box's own streaming copy rate (box-to-box
-            # HBM / clock spread divides out): Mpix/s per GB/s of measured device copy
-            out["value_per_copy_gbs"] = round(value / floors["device_copy_gbs"], 5)
-        if not args.no_extras and world == 1:
-            out["extra_configs"] = {"4k_rgb_encode": extra_4k_rgb_encode(),
-                                    "3840x2160_rgb_encode": extra_ragged_rgb_encode(2160, 3840),
-                                    # 1080 rows are not a multiple of 16 (the fused kernel's unit): 1088
-                                    "1920x1088_rgb_encode": extra_ragged_rgb_encode(1088, 1920),
-                                    "4k_luma_dct": extra_4k_luma(
-                                        floor_us=floors["luma_pattern"]["4k_luma"]["median_launch_us"]),
-                                    "8k_plane_dct": extra_8k_plane_dct(),
-                                    "8k_luma_dct": extra_8k_plane_dct(
-                                        luma_only=True, floor_us=floors["luma_pattern"]["1x"]["median_launch_us"]),
-                                    "8k_luma_dct_back_to_back": extra_8k_luma_batched(
-                                        floor_us_per_plane=round(floors["luma_pattern"]["4x"]["median_launch_us"] / 4,
-                                                                 2)),
-                                    "8k_jpeg_decode": extra_8k_jpeg_decode(),
-                                    "8k_encode_from_host": extra_8k_encode_from_host(),
-                                    "16k_roundtrip": extra_16k_roundtrip(),
-                                    "8k_reference_api": extra_8k_reference_api()}
-        if extra_sharded is not None:
-            out["extra_configs"] = {"16k_roundtrip": extra_sharded}
-        if not args.no_cpu_baseline and world == 1:
-            out["cpu_baseline"] = cpu_baseline(args.cpu_budget_s)
-        elif not args.no_cpu_baseline:
-            out["cpu_baseline"] = None
+            }
+            if world == 1:
+                floors = measure_floors(slots=slots)
+                out["memory_floors"] = floors
+                out["roofline"]["device_copy_gbs"] = floors["device_copy_gbs"]
+                out["roofline"]["frac_of_device_copy"] = round(achieved / floors["device_copy_gbs"], 4)
+                if fused and args.workload == "8k":
+                    # the kernel's own byte pattern without its arithmetic, measured in this run
+                    fl = floors["encode420_pattern"]["median_launch_us"]
+                    out["roofline"]["memory_floor_us"] = fl
+                    out["roofline"]["frac_of_memory_floor"] = round(fl / dct_us, 4)
+                    out["roofline"]["memory_floor_source"] = ("memory_floors.encode420_pattern (%s, this run)" %
+                                                              ("hic_probe_encode420_slots" if slots else
+                                                               "hic_probe_encode420"))
+                # the headline normalised by this box's own streaming copy rate (box-to-box
+                # HBM / clock spread divides out): Mpix/s per GB/s of measured device copy
+                out["value_per_copy_gbs"] = round(value / floors["device_copy_gbs"], 5)
+            if not args.no_extras and world == 1:
+                out["extra_configs"] = {"4k_rgb_encode": extra_4k_rgb_encode(),
+                                        "3840x2160_rgb_encode": extra_ragged_rgb_encode(2160, 3840),
+                                        # 1080 rows are not a multiple of 16 (the fused kernel's unit): 1088
+                                        "1920x1088_rgb_encode": extra_ragged_rgb_encode(1088, 1920),
+                                        "4k_luma_dct": extra_4k_luma(
+                                            floor_us=floors["luma_pattern"]["4k_luma"]["median_launch_us"]),
+                                        "8k_plane_dct": extra_8k_plane_dct(),
+                                        "8k_luma_dct": extra_8k_plane_dct(
+                                            luma_only=True, floor_us=floors["luma_pattern"]["1x"]["median_launch_us"]),
+                                        "8k_luma_dct_back_to_back": extra_8k_luma_batched(
+                                            floor_us_per_plane=round(floors["luma_pattern"]["4x"]["median_launch_us"] / 4,
+                                                                     2)),
+                                        "8k_jpeg_decode": extra_8k_jpeg_decode(),
+                                        "8k_encode_from_host": extra_8k_encode_from_host(),
+                                        "16k_roundtrip": extra_16k_roundtrip(),
+                                        "8k_reference_api": extra_8k_reference_api()}
+            if extra_sharded is not None:
+                out["extra_configs"] = {"16k_roundtrip": extra_sharded}
+            if not args.no_cpu_baseline and world == 1:
+                out["cpu_baseline"] = cpu_baseline(args.cpu_budget_s)
+            elif not args.no_cpu_baseline:
+                out["cpu_baseline"] = None
         print(json.dumps(out), flush=True)
     if rgather is not None:
         torch.cuda.synchronize()

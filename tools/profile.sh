@@ -30,12 +30,12 @@ final)
   tail -3 $out/gputest.log
   timeout -k 10 120 python -u -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.log 2>&1 || { cat $out/smoke.log; exit 1; }
   grep -v amdgpu.ids $out/smoke.log
-  timeout -k 10 500 python -u bench.py > $out/bench_default.json 2>&1 || { tail -20 $out/bench_default.json; exit 1; }
+  timeout -k 10 500 python -u bench.py --full > $out/bench_default.json 2>&1 || { tail -20 $out/bench_default.json; exit 1; }
   grep '^{' $out/bench_default.json | tail -1 | cut -c1-600
   ;;
 trace)
   prof timeout -k 10 500 rocprofv3 --kernel-trace --stats -d $out/trace_default -o run --output-format csv -- \
-    python3 bench.py --no-cpu-baseline > $out/trace_default.json.log 2>&1 || { tail -5 $out/trace_default.json.log; exit 1; }
+    python3 bench.py --full --no-cpu-baseline > $out/trace_default.json.log 2>&1 || { tail -5 $out/trace_default.json.log; exit 1; }
   python3 tools/trace_launches.py $out/trace_default/run_kernel_trace.csv k_dct > $out/trace_default_dct_launches.txt
   python3 tools/trace_launches.py $out/trace_default/run_kernel_trace.csv k_encode420 k_rle k_rld > \
     $out/trace_default_encode_launches.txt
@@ -44,7 +44,7 @@ trace)
 pmc)
   hipcc --offload-arch=gfx950 -O3 -o $out/cal_patterns tools/micro/cal_patterns.hip
   timeout -k 10 120 $out/cal_patterns > $out/cal_patterns.log 2>&1 || exit 1
-  B="python3 bench.py --steps 12 --warmup 4 --no-cpu-baseline --no-extras --streams 1 ${PROF_ARGS:-}"
+  B="python3 bench.py --full --steps 12 --warmup 4 --no-cpu-baseline --no-extras --streams 1 ${PROF_ARGS:-}"
   prof timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $out/trace -o run --output-format csv -- $B \
     > $out/trace.json.log 2>&1 || { tail -5 $out/trace.json.log; exit 1; }
   for c in FETCH_SIZE WRITE_SIZE; do
