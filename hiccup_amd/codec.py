@@ -439,6 +439,94 @@ def _decode_channel_start(dc, lens, vals, n, shape, bs):
     return raster, check
 
 
+# ------------------------------------------------------------------ one-call surface
+def encode(rgb_image):
+    """H x W x 3 uint8 image (a numpy array or a device tensor) -> HicImage, ==
+    jpeg_encode(compression.jpeg_compression(rgb_image)) byte for byte, on the
+    device-resident path: one upload, pipeline.Encoder's own layout for the shape
+    (slot layout, fused kernel, or the chain for ragged shapes) and the Huffman
+    stage straight from the encoder's streams (Encoder.hic_image(from_slots=True)).
+    A shape the pipeline refuses goes through the two calls themselves."""
+    with _gc_paused():
+        return _encode(rgb_image)
+
+
+def _encode(rgb_image):
+    from . import compression, pipeline
+    on_device = isinstance(rgb_image, torch.Tensor)
+    rgb = rgb_image if on_device else np.asarray(rgb_image)
+    if rgb.ndim != 3 or rgb.shape[2] != 3 or rgb.dtype != (torch.uint8 if on_device else np.uint8):
+        raise ValueError("encode expects an H x W x 3 uint8 image")
+    H, W = int(rgb.shape[0]), int(rgb.shape[1])
+    if settings.JPEG_BLOCK_SIZE != 8 or H < 2 or W < 2:
+        return _jpeg_encode(compression.jpeg_compression(rgb.cpu().numpy() if on_device else rgb))
+    x = rgb.contiguous() if on_device else device.to_device(rgb)
+    enc = pipeline.Encoder(H, W)
+    enc.encode(x)
+    return enc.hic_image(from_slots=True)
+
+
+def decode(hic_image):
+    """HicImage -> RGB uint8 numpy array, == compression.jpeg_decompression(
+    jpeg_decode(hic_image)), without the float64 planes' round trip through the
+    host: the nine streams are Huffman-decoded on the device (as jpeg_decode does),
+    narrowed there to the pipeline's uint8 / int16 symbols and decoded by
+    pipeline.Decoder; one copy back of the RGB.  Anything outside what an encoder
+    writes -- a block size other than 8, a table that is not a complete int32 prefix
+    code, a length outside 0..255, a value or DC outside int16, planes that are not
+    whole 8 x 8 blocks (jpeg_decode asserts on those), shapes or counts that do not
+    fit, a stream that does not cover its blocks -- goes through the two calls
+    themselves, with their results and exceptions."""
+    with _gc_paused():
+        return _decode(hic_image)
+
+
+def _decode(hic_image):
+    from . import compression, pipeline
+
+    def chained():
+        return compression.jpeg_decompression(_jpeg_decode(hic_image))
+
+    p = hic_image.payloads
+    if settings.JPEG_BLOCK_SIZE != 8 or hic_image.hic_type != model.Compression.JPEG or len(p) != 20:
+        return chained()
+    trees = [huffman.FlatCodes.from_table([q.numbers for q in p[i].payloads]) for i in range(9)]
+    if any(t is None for t in trees):
+        return chained()
+    try:
+        (H, W), (h, w) = (tuple(int(v) for v in p[i].numbers) for i in (18, 19))
+    except (TypeError, ValueError):
+        return chained()
+    if H < 2 or W < 2 or (h, w) != (H // 2, W // 2) or (H, W) != tuple(p[18].numbers) or (h, w) != tuple(p[19].numbers):
+        return chained()
+    if H % 16 or W % 16:
+        # a plane that is not whole 8 x 8 blocks: jpeg_decode's length assertions
+        # (codec.py:418) are evaluated on the symbols themselves there
+        return chained()
+    streams = _huffman_streams_device([p[9 + i] for i in range(9)], trees)
+    sym_len, sym_val, dc, counts, lims = {}, {}, {}, [], []
+    for c, k in enumerate(pipeline.CHANNELS):
+        (D, nd), (V, nv), (L, nl) = streams[c], streams[3 + c], streams[6 + c]
+        nblk = pipeline._nblk(*((H, W) if k == "lum" else (h, w)))
+        if nd != nblk or nv != nl or nv < 1:
+            return chained()
+        D, V, L = D[:nd], V[:nv], L[:nl]
+        # >= 0 when in range: lengths 0..255, values int16, the running DC within +-32767
+        lims += [L.min().long(), 255 - L.max().long(), V.min().long() + 32768, 32767 - V.max().long(),
+                 32767 - torch.cumsum(D, 0, dtype=torch.int64).abs().max()]
+        sym_len[k], sym_val[k], dc[k] = L.to(torch.uint8), V.to(torch.int16), D.contiguous()
+        counts.append(nv)
+    if int(torch.stack(lims).min().cpu()) < 0:  # one read for the fifteen range checks
+        return chained()
+    dec = pipeline.Decoder(H, W)
+    rgb = dec.decode(sym_len, sym_val, counts, dc)
+    try:
+        dec.check_status()
+    except ValueError:
+        return chained()
+    return device.to_host(rgb)
+
+
 # ------------------------------------------------------------------ out of scope
 def wavelet_encode(compressed):
     raise NotImplementedError(_OUT_OF_SCOPE)

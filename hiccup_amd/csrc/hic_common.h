@@ -78,6 +78,10 @@ int rle_tile16_launch(const int16_t *blocks, int64_t nblk, int max_len, int64_t 
 // its records' last DCs (int32 per record) start, after the scan's records,
 // offsets and hand-off granules; and the job's record count.
 int64_t slot_rdc_word(int64_t nrec);
+// The int64 word of an RLE / slot job's workspace where the scan's offsets start,
+// after the 3-word records: offs[2 r] = record r's offset in the symbol stream,
+// offs[2 r + 1] = the AC position of the last nonzero before it.
+__host__ __device__ inline int64_t rle_offs_word(int64_t nrec) { return 3 * nrec; }
 inline int64_t slot_nrec(int64_t nblk, int64_t records_per_tile) {
   return (nblk * records_per_tile + 63) / 64;
 }

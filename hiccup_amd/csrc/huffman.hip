@@ -19,6 +19,10 @@
 //                     words shared with neighbouring tiles OR-ed in; *d_nbits = total
 //                     bits (words past out_bytes are not written: the caller sizes
 //                     the buffer from the histogram, sum of count x code length)
+//  hic_slot_key_range / hic_slot_key_histogram / hic_slot_huffman_pack
+//                     the same three steps over channels still in the slot layout
+//                     (slots.h), every channel in one grid per phase and no compaction
+//                     (the second half of this file)
 #include "hic_common.h"
 
 namespace hic {
@@ -28,6 +32,7 @@ constexpr int kHT = 256;                  // threads per workgroup
 constexpr int kHPT = 16;                  // symbols per thread
 constexpr int kHTile = kHT * kHPT;        // symbols per tile
 constexpr int kHistLds = 8192;            // bins held in LDS
+constexpr int kSlotCapMax = 64 * 63;      // symbols of the largest slot (slots.h)
 
 __device__ __forceinline__ int key_at(const void *keys, int kb, int64_t i) {
   if (kb == 1) return (int)static_cast<const uint8_t *>(keys)[i];
@@ -205,7 +210,7 @@ __global__ __launch_bounds__(kHT) void k_pack_sizes(const void *__restrict__ key
 }
 
 // in-place exclusive scan of n int64 by one workgroup; *total = the sum
-__global__ __launch_bounds__(kHT) void k_pack_scan(int64_t *__restrict__ v, int64_t n, int64_t *__restrict__ total) {
+__device__ __forceinline__ void scan_in_place(int64_t *__restrict__ v, int64_t n, int64_t *__restrict__ total) {
   __shared__ int64_t s_w[kHT / 64];
   int64_t run = 0;
   for (int64_t c0 = 0; c0 < n; c0 += kHT) {
@@ -218,6 +223,9 @@ __global__ __launch_bounds__(kHT) void k_pack_scan(int64_t *__restrict__ v, int6
   }
   if (threadIdx.x == 0) *total = run;
 }
+__global__ __launch_bounds__(kHT) void k_pack_scan(int64_t *__restrict__ v, int64_t n, int64_t *__restrict__ total) {
+  scan_in_place(v, n, total);
+}
 
 __device__ __forceinline__ uint32_t bswap32(uint32_t x) { return __builtin_bswap32(x); }
 
@@ -226,25 +234,17 @@ __device__ __forceinline__ uint32_t bswap32(uint32_t x) { return __builtin_bswap
 // the first / last word OR-ed atomically (shared with the neighbouring tiles).
 // out must be zeroed; its words are big-endian bit runs.
 constexpr int kPackWords = kHTile * 64 / 32 + 2;  // 64-bit codes at most
-__global__ __launch_bounds__(kHT) void k_pack_bits(const void *__restrict__ keys, int kb, int64_t n, int key_min,
-                                                   int nbins, const uint64_t *__restrict__ code_bits,
-                                                   const uint8_t *__restrict__ code_len,
-                                                   const int64_t *__restrict__ tile_off, uint32_t *__restrict__ out,
-                                                   int64_t out_words) {
-  extern __shared__ uint32_t s_words[];
-  __shared__ int64_t s_w[kHT / 64];
-  const int64_t s0 = (int64_t)blockIdx.x * kHTile + (int64_t)threadIdx.x * kHPT;
-  int ks[kHPT];
+// one tile: ks = each thread's kHPT table indices in stream order (-1: codes to
+// nothing), B0 = the tile's first bit.  Every thread of the workgroup must call it.
+__device__ __forceinline__ void pack_tile(const int (&ks)[kHPT], const uint64_t *__restrict__ code_bits,
+                                          const uint8_t *__restrict__ code_len, int64_t B0,
+                                          uint32_t *__restrict__ out, int64_t out_words, uint32_t *s_words,
+                                          int64_t *s_w) {
   int64_t acc = 0;
 #pragma unroll
-  for (int k = 0; k < kHPT; ++k) {
-    ks[k] = s0 + k < n ? key_at(keys, kb, s0 + k) - key_min : -1;
-    if ((unsigned)ks[k] >= (unsigned)nbins) ks[k] = -1;
-    acc += ks[k] >= 0 ? code_len[ks[k]] : 0;
-  }
+  for (int k = 0; k < kHPT; ++k) acc += ks[k] >= 0 ? code_len[ks[k]] : 0;
   int64_t tile_total;
   const int64_t my = blk_excl_sum(acc, s_w, tile_total);
-  const int64_t B0 = tile_off[blockIdx.x];      // the tile's first bit
   const int64_t w0 = B0 >> 5;                    // its first (global) word
   const int nwords = (int)(((B0 + tile_total + 31) >> 5) - w0);
   for (int i = threadIdx.x; i < nwords; i += kHT) s_words[i] = 0;
@@ -277,6 +277,361 @@ __global__ __launch_bounds__(kHT) void k_pack_bits(const void *__restrict__ keys
     } else {
       out[w0 + i] = v;
     }
+  }
+}
+__global__ __launch_bounds__(kHT) void k_pack_bits(const void *__restrict__ keys, int kb, int64_t n, int key_min,
+                                                   int nbins, const uint64_t *__restrict__ code_bits,
+                                                   const uint8_t *__restrict__ code_len,
+                                                   const int64_t *__restrict__ tile_off, uint32_t *__restrict__ out,
+                                                   int64_t out_words) {
+  extern __shared__ uint32_t s_words[];
+  __shared__ int64_t s_w[kHT / 64];
+  const int64_t s0 = (int64_t)blockIdx.x * kHTile + (int64_t)threadIdx.x * kHPT;
+  int ks[kHPT];
+#pragma unroll
+  for (int k = 0; k < kHPT; ++k) {
+    ks[k] = s0 + k < n ? key_at(keys, kb, s0 + k) - key_min : -1;
+    if ((unsigned)ks[k] >= (unsigned)nbins) ks[k] = -1;
+  }
+  pack_tile(ks, code_bits, code_len, tile_off[blockIdx.x], out, out_words, s_words, s_w);
+}
+
+// ---------------------------------------------------------------------------
+// The same three steps over channels still in the slot layout (slots.h), with no
+// compaction: a channel's "virtual stream" -- what hic_rle_slots_compact would
+// write -- is, over its records r in order, nfill_r fillers (M - 1, 0) at stream
+// offset offs_r, then slot r's n_r symbols, then the EOB (0, 0) when the count says
+// there is one.  The EOB is handled as one more symbol of the LAST record (index
+// n_r: a record whose every AC position is a symbol ends in a nonzero and has no
+// EOB, so n_r + 1 never exceeds the slot).  Each channel gives two key streams:
+// 0 = lengths (1-byte keys), 1 = values (2-byte keys); all kernels take every
+// channel in one grid (blockIdx.y = the channel).
+struct HsJob {
+  const uint8_t *slot_len;
+  const int16_t *slot_val;
+  const int32_t *sidx;     // the close's {n, P, pdc, nfill} per record
+  const int64_t *offs;     // the scan's offs[2 r] = record r's stream offset
+  const int64_t *d_count;
+  int64_t nrec;
+  int capr;                // slot capacity (symbols): 4032 or 2016, whole 16-byte chunks
+  int key_min[2], nbins[2];
+  uint32_t *cnt[2], *first[2];
+  uint32_t *part;          // histogram: per-workgroup bins [gridDim.x][2][nbins[0] + nbins[1]]; null: global atomics
+  const uint64_t *cbits[2];
+  const uint8_t *clen[2];
+  uint32_t *out[2];
+  int64_t out_words[2];
+  int64_t *bits[2];        // per record: its bit size (pass A), then its first bit (the scan)
+  int64_t *d_nbits;        // [2]
+};
+struct HsJobs {
+  HsJob j[3];
+  int n, M;
+};
+static_assert(kSlotCapMax <= kHTile, "a slot fits one pack tile");
+
+// record r: its slot symbols n, those plus the EOB ne, its fillers and stream offset
+__device__ __forceinline__ void hs_record(const HsJob &J, int64_t r, int &n, int &ne, int &nf, int64_t &off) {
+  const int4 ix = *reinterpret_cast<const int4 *>(J.sidx + 4 * r);
+  n = ix.x;
+  nf = ix.w;
+  off = J.offs[2 * r];
+  ne = n + ((r == J.nrec - 1 && *J.d_count == off + nf + n + 1) ? 1 : 0);
+}
+
+// the keys of symbols 16 c .. 16 c + 15 of record r in stream S (16-byte loads; the
+// EOB's key is 0); returns how many of them exist (0..16)
+template <int S>
+__device__ __forceinline__ int hs_keys16(const HsJob &J, int64_t r, int c, int n, int ne, int (&key)[16]) {
+  const int m = ne - 16 * c < 16 ? ne - 16 * c : 16;
+  if (m <= 0) return 0;
+  if (S == 0) {
+    const uint4 q = reinterpret_cast<const uint4 *>(J.slot_len + r * J.capr)[c];
+    const uint32_t w[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+    for (int k = 0; k < 16; ++k) key[k] = (int)((w[k >> 2] >> (8 * (k & 3))) & 0xFFu);
+  } else {
+    const uint4 *p = reinterpret_cast<const uint4 *>(J.slot_val + r * J.capr) + 2 * c;
+    const uint4 q0 = p[0], q1 = p[1];
+    const uint32_t w[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
+#pragma unroll
+    for (int k = 0; k < 16; ++k) key[k] = (int)(int16_t)(w[k >> 1] >> (16 * (k & 1)));
+  }
+#pragma unroll
+  for (int k = 0; k < 16; ++k)
+    if (16 * c + k >= n) key[k] = 0;
+  return m;
+}
+
+// d_minmax[4 y .. 4 y + 3] = channel y's {min, max} of the lengths, of the values
+__global__ __launch_bounds__(kHT) void k_slot_range(HsJobs jobs, int *__restrict__ mm) {
+  __shared__ int s_r[4][kHT / 64];
+  const HsJob &J = jobs.j[blockIdx.y];
+  const int64_t a = J.nrec * blockIdx.x / gridDim.x, b = J.nrec * (blockIdx.x + 1) / gridDim.x;
+  int v[4] = {2147483647, -2147483647 - 1, 2147483647, -2147483647 - 1};
+  auto see = [&](int s, int k) {
+    v[2 * s] = k < v[2 * s] ? k : v[2 * s];
+    v[2 * s + 1] = k > v[2 * s + 1] ? k : v[2 * s + 1];
+  };
+  for (int64_t r = a; r < b; ++r) {
+    int n, ne, nf;
+    int64_t off;
+    hs_record(J, r, n, ne, nf, off);
+    if (nf > 0) {
+      see(0, jobs.M - 1);
+      see(1, 0);
+    }
+    for (int c = threadIdx.x; 16 * c < ne; c += kHT) {
+      int key[16];
+      int m = hs_keys16<0>(J, r, c, n, ne, key);
+#pragma unroll
+      for (int k = 0; k < 16; ++k)
+        if (k < m) see(0, key[k]);
+      m = hs_keys16<1>(J, r, c, n, ne, key);
+#pragma unroll
+      for (int k = 0; k < 16; ++k)
+        if (k < m) see(1, key[k]);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+      const int o = __shfl_xor(v[i], d, 64);
+      v[i] = (i & 1) ? (o > v[i] ? o : v[i]) : (o < v[i] ? o : v[i]);
+    }
+    if ((threadIdx.x & 63) == 0) s_r[i][threadIdx.x >> 6] = v[i];
+  }
+  __syncthreads();
+  if (threadIdx.x < 4) {  // one atomic per workgroup and value (k_key_range)
+    const int i = threadIdx.x;
+    int x = s_r[i][0];
+    for (int w = 1; w < kHT / 64; ++w) x = (i & 1) ? (s_r[i][w] > x ? s_r[i][w] : x) : (s_r[i][w] < x ? s_r[i][w] : x);
+    if (i & 1)
+      atomicMax(mm + 4 * blockIdx.y + i, x);
+    else
+      atomicMin(mm + 4 * blockIdx.y + i, x);
+  }
+}
+
+// per bin the count and the first position in the virtual stream.  LDS bins (the
+// channel's lengths then its values, <= kHistLds together) stored per workgroup to J.part for
+// k_slot_hist_reduce, as k_key_hist does; a channel whose bins exceed the LDS
+// (J.part null) adds into the zero / 0xFFFFFFFF initialised outputs.
+__global__ __launch_bounds__(kHT) void k_slot_hist(HsJobs jobs) {
+  __shared__ uint32_t s_cnt[kHistLds], s_first[kHistLds];
+  const HsJob &J = jobs.j[blockIdx.y];
+  const bool lds = J.part != nullptr;
+  const int nb0 = J.nbins[0], nbt = nb0 + J.nbins[1];
+  if (lds) {
+    for (int b = threadIdx.x; b < nbt; b += kHT) {
+      s_cnt[b] = 0;
+      s_first[b] = 0xFFFFFFFFu;
+    }
+    __syncthreads();
+  }
+  auto add = [&](int s, int key, uint32_t c, uint32_t pos) {
+    const int b = key - J.key_min[s];
+    if ((unsigned)b >= (unsigned)J.nbins[s]) return;  // outside the caller's range: not counted
+    if (lds) {
+      const int x = s ? nb0 + b : b;
+      atomicAdd(&s_cnt[x], c);
+      if (pos < s_first[x]) atomicMin(&s_first[x], pos);
+    } else {
+      atomicAdd(&J.cnt[s][b], c);
+      atomicMin(&J.first[s][b], pos);
+    }
+  };
+  const int64_t a = J.nrec * blockIdx.x / gridDim.x, e = J.nrec * (blockIdx.x + 1) / gridDim.x;
+  for (int64_t r = a; r < e; ++r) {
+    int n, ne, nf;
+    int64_t off;
+    hs_record(J, r, n, ne, nf, off);
+    if (nf > 0 && threadIdx.x == 0) {  // the filler run: nf of one key, first at the record's offset
+      add(0, jobs.M - 1, (uint32_t)nf, (uint32_t)off);
+      add(1, 0, (uint32_t)nf, (uint32_t)off);
+    }
+    for (int c = threadIdx.x; 16 * c < ne; c += kHT) {
+      const uint32_t p0 = (uint32_t)(off + nf + 16 * c);
+      int key[16];
+      int m = hs_keys16<0>(J, r, c, n, ne, key);
+#pragma unroll
+      for (int k = 0; k < 16; ++k)
+        if (k < m) add(0, key[k], 1u, p0 + k);
+      m = hs_keys16<1>(J, r, c, n, ne, key);
+#pragma unroll
+      for (int k = 0; k < 16; ++k)
+        if (k < m) add(1, key[k], 1u, p0 + k);
+    }
+  }
+  if (lds) {
+    __syncthreads();
+    uint32_t *pc = J.part + (int64_t)blockIdx.x * 2 * nbt;
+    for (int b = threadIdx.x; b < nbt; b += kHT) {
+      pc[b] = s_cnt[b];
+      pc[nbt + b] = s_first[b];
+    }
+  }
+}
+
+// the sum / min of a channel's nwg partial bins into its two streams' outputs
+__global__ __launch_bounds__(kHT) void k_slot_hist_reduce(HsJobs jobs, int nwg) {
+  const HsJob &J = jobs.j[blockIdx.y];
+  const int nb0 = J.nbins[0], nbt = nb0 + J.nbins[1];
+  const int b = blockIdx.x * kHT + threadIdx.x;
+  if (!J.part || b >= nbt) return;
+  uint32_t c = 0, f = 0xFFFFFFFFu;
+  for (int w = 0; w < nwg; ++w) {
+    const uint32_t *pc = J.part + (int64_t)w * 2 * nbt;
+    c += pc[b];
+    f = pc[nbt + b] < f ? pc[nbt + b] : f;
+  }
+  const int s = b >= nb0, x = s ? b - nb0 : b;
+  J.cnt[s][x] = c;
+  J.first[s][x] = f;
+}
+
+// a stream's filler code: (length, bits) of key `key`; length 0 outside the table
+__device__ __forceinline__ int hs_fill_code(const HsJob &J, int s, int key, uint64_t &bits) {
+  const int b = key - J.key_min[s];
+  if ((unsigned)b >= (unsigned)J.nbins[s]) return 0;
+  bits = J.cbits[s][b];
+  return J.clen[s][b];
+}
+
+// the 16 table indices (-1: codes to nothing) of thread t's symbols of record r
+template <int S>
+__device__ __forceinline__ void hs_index16(const HsJob &J, int64_t r, int n, int ne, int (&ks)[kHPT]) {
+  static_assert(kHPT == 16, "one 16-byte chunk of lengths per thread");
+  const int m = hs_keys16<S>(J, r, threadIdx.x, n, ne, ks);
+#pragma unroll
+  for (int k = 0; k < kHPT; ++k) {
+    const int b = ks[k] - J.key_min[S];
+    ks[k] = (k < m && (unsigned)b < (unsigned)J.nbins[S]) ? b : -1;
+  }
+}
+
+// pack pass A: one workgroup per record: the bits of its fillers + its symbols, both streams
+__global__ __launch_bounds__(kHT) void k_slot_pack_sizes(HsJobs jobs) {
+  __shared__ int64_t s_w[kHT / 64];
+  const HsJob &J = jobs.j[blockIdx.y];
+  const int64_t r = blockIdx.x;
+  if (r >= J.nrec) return;
+  int n, ne, nf;
+  int64_t off;
+  hs_record(J, r, n, ne, nf, off);
+  int ks[kHPT];
+  uint32_t a0 = 0, a1 = 0;  // <= 4032 x 64 bits each
+  hs_index16<0>(J, r, n, ne, ks);
+#pragma unroll
+  for (int k = 0; k < kHPT; ++k) a0 += ks[k] >= 0 ? J.clen[0][ks[k]] : 0;
+  hs_index16<1>(J, r, n, ne, ks);
+#pragma unroll
+  for (int k = 0; k < kHPT; ++k) a1 += ks[k] >= 0 ? J.clen[1][ks[k]] : 0;
+  int64_t total;
+  blk_excl_sum((int64_t)a0 | ((int64_t)a1 << 32), s_w, total);
+  if (threadIdx.x == 0) {
+    uint64_t c;
+    J.bits[0][r] = (int64_t)nf * hs_fill_code(J, 0, jobs.M - 1, c) + (total & 0xFFFFFFFFll);
+    J.bits[1][r] = (int64_t)nf * hs_fill_code(J, 1, 0, c) + (total >> 32);
+  }
+}
+
+// the records' first bits: one workgroup per stream
+__global__ __launch_bounds__(kHT) void k_slot_pack_scan(HsJobs jobs) {
+  const HsJob &J = jobs.j[blockIdx.y];
+  scan_in_place(J.bits[blockIdx.x], J.nrec, J.d_nbits + blockIdx.x);
+}
+
+// pack pass B: one workgroup per record packs its slot's symbols (after its fillers'
+// bits, which k_slot_pack_fill writes) as one tile of each stream
+__global__ __launch_bounds__(kHT) void k_slot_pack_bits(HsJobs jobs) {
+  extern __shared__ uint32_t s_words[];
+  __shared__ int64_t s_w[kHT / 64];
+  const HsJob &J = jobs.j[blockIdx.y];
+  const int64_t r = blockIdx.x;
+  if (r >= J.nrec) return;
+  int n, ne, nf;
+  int64_t off;
+  hs_record(J, r, n, ne, nf, off);
+  if (ne == 0) return;
+  int ks[kHPT];
+  uint64_t c;
+  hs_index16<0>(J, r, n, ne, ks);
+  pack_tile(ks, J.cbits[0], J.clen[0], J.bits[0][r] + (int64_t)nf * hs_fill_code(J, 0, jobs.M - 1, c), J.out[0],
+            J.out_words[0], s_words, s_w);
+  hs_index16<1>(J, r, n, ne, ks);
+  pack_tile(ks, J.cbits[1], J.clen[1], J.bits[1][r] + (int64_t)nf * hs_fill_code(J, 1, 0, c), J.out[1],
+            J.out_words[1], s_words, s_w);
+}
+
+// word i of a filler run: nbits bits from bit F0 of the stream, the code (c, clen)
+// repeated.  Words the run covers whole are stored, its edge words OR-ed in.
+__device__ __forceinline__ void hs_fill_word(uint32_t *__restrict__ out, int64_t out_words, int64_t F0, int64_t nbits,
+                                             uint64_t c, int clen, int64_t i) {
+  const int64_t w = (F0 >> 5) + i;
+  if (w >= out_words) return;
+  const int64_t q0 = (w << 5) - F0;  // the run offset of the word's first bit (< 0 in the first word)
+  const int64_t end = q0 + 32 < nbits ? q0 + 32 : nbits;
+  int64_t q = q0 > 0 ? q0 : 0;
+  int ph = (int)(q % clen);  // bits of the current code already behind q
+  uint32_t v = 0;
+  while (q < end) {
+    int take = clen - ph;
+    if (take > end - q) take = (int)(end - q);  // <= 32
+    const uint32_t piece = (uint32_t)((c >> (clen - ph - take)) & (take == 32 ? 0xFFFFFFFFull : ((1ull << take) - 1)));
+    v |= piece << (32 - (int)(q - q0) - take);
+    q += take;
+    ph = 0;
+  }
+  v = bswap32(v);
+  if (q0 < 0 || q0 + 32 > nbits) {
+    if (v) atomicOr(&out[w], v);
+  } else {
+    out[w] = v;
+  }
+}
+
+// the filler runs' bits.  Every workgroup of a channel walks its records' nfill in
+// batches of kHT; a short run (<= kFillShort words) is written by its thread in the
+// batch's own workgroup (batches dealt round-robin), a long one -- a carried zero run
+// can span nearly the whole channel -- word by word by ALL the channel's workgroups.
+constexpr int kFillShort = 16;
+__global__ __launch_bounds__(kHT) void k_slot_pack_fill(HsJobs jobs) {
+  __shared__ int s_list[2 * kHT];
+  __shared__ int s_nlist;
+  const HsJob &J = jobs.j[blockIdx.y];
+  uint64_t fc[2] = {0, 0};
+  const int fl[2] = {hs_fill_code(J, 0, jobs.M - 1, fc[0]), hs_fill_code(J, 1, 0, fc[1])};
+  if (fl[0] == 0 && fl[1] == 0) return;  // no filler in the tables: no run
+  for (int64_t r0 = 0, bt = 0; r0 < J.nrec; r0 += kHT, ++bt) {
+    if (threadIdx.x == 0) s_nlist = 0;
+    __syncthreads();
+    const int64_t r = r0 + threadIdx.x;
+    const int nf = r < J.nrec ? J.sidx[4 * r + 3] : 0;
+    if (nf > 0) {
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        if (fl[s] == 0) continue;
+        const int64_t F0 = J.bits[s][r], nbits = (int64_t)nf * fl[s];
+        const int64_t nw = ((F0 + nbits + 31) >> 5) - (F0 >> 5);
+        if (nw > kFillShort)
+          s_list[atomicAdd(&s_nlist, 1)] = 2 * threadIdx.x + s;
+        else if (bt % gridDim.x == blockIdx.x)
+          for (int64_t i = 0; i < nw; ++i) hs_fill_word(J.out[s], J.out_words[s], F0, nbits, fc[s], fl[s], i);
+      }
+    }
+    __syncthreads();
+    const int nl = s_nlist;
+    for (int e = 0; e < nl; ++e) {
+      const int s = s_list[e] & 1;
+      const int64_t rr = r0 + (s_list[e] >> 1);
+      const int64_t F0 = J.bits[s][rr], nbits = (int64_t)J.sidx[4 * rr + 3] * fl[s];
+      const int64_t nw = ((F0 + nbits + 31) >> 5) - (F0 >> 5);
+      for (int64_t i = (int64_t)blockIdx.x * kHT + threadIdx.x; i < nw; i += (int64_t)gridDim.x * kHT)
+        hs_fill_word(J.out[s], J.out_words[s], F0, nbits, fc[s], fl[s], i);
+    }
+    __syncthreads();
   }
 }
 
@@ -368,4 +723,176 @@ extern "C" int hic_huffman_pack(const void *keys, int key_bytes, int64_t n, int3
                      n, key_min, nbins, d_code_bits, d_code_len, tile, reinterpret_cast<uint32_t *>(out),
                      out_bytes / 4);
   return check_launch("k_pack_bits");
+}
+
+// ---- the slot layout's streams (the kernels' comment above) ----
+// hic_slot_job[n] -> the kernels' jobs; everything is checked before any device call
+static int hs_jobs(int n, const hic_slot_job *jobs, int max_len, HsJobs &J, int64_t &max_nrec) {
+  if (n < 1 || n > 3 || !jobs) return arg_error("1 <= n <= 3 jobs");
+  if (max_len != 15) return arg_error("the slot layout needs max_len 15");
+  J = HsJobs{};
+  J.n = n;
+  J.M = max_len;
+  max_nrec = 0;
+  for (int k = 0; k < n; ++k) {
+    const hic_slot_job &a = jobs[k];
+    if (!a.slot_len || !a.slot_val || !a.d_index || !a.workspace || !a.d_count) return arg_error("job %d: null pointer", k);
+    // (a stream holds at most nblk * 63 + 1 symbols: positions fit 32 bits)
+    if (a.nblk <= 0 || a.nblk > (int64_t)INT32_MAX / 63) return arg_error("job %d: nblk", k);
+    if (a.records_per_tile != 1 && a.records_per_tile != 2) return arg_error("job %d: records_per_tile must be 1 or 2", k);
+    const int64_t bpr = 64 / a.records_per_tile;
+    if (a.nblk % bpr) return arg_error("job %d: nblk must be a multiple of %lld (whole records)", k, (long long)bpr);
+    if ((reinterpret_cast<uintptr_t>(a.slot_len) | reinterpret_cast<uintptr_t>(a.slot_val) |
+         reinterpret_cast<uintptr_t>(a.d_index)) % 16)
+      return arg_error("job %d: slot arrays and index must be 16-byte aligned", k);
+    if (a.workspace_bytes < (int64_t)hic_rle_slots_workspace_bytes(a.nblk, (int)a.records_per_tile))
+      return arg_error("job %d: workspace too small", k);
+    HsJob &j = J.j[k];
+    j.slot_len = a.slot_len;
+    j.slot_val = a.slot_val;
+    j.sidx = a.d_index;
+    j.nrec = slot_nrec(a.nblk, a.records_per_tile);
+    j.offs = static_cast<const int64_t *>(a.workspace) + rle_offs_word(j.nrec);
+    j.d_count = a.d_count;
+    j.capr = (int)(63 * bpr);
+    max_nrec = j.nrec > max_nrec ? j.nrec : max_nrec;
+  }
+  return HIC_OK;
+}
+
+// hipMemsetAsync of m <= 6 regions, in address order with touching neighbours merged
+// into one call (the six AC streams' outputs of one image are one block)
+static int memset_regions(int m, uint8_t *const *p, const int64_t *bytes, int value, hipStream_t s) {
+  int idx[6];
+  for (int i = 0; i < m; ++i) {
+    int k = i;
+    for (; k > 0 && p[idx[k - 1]] > p[i]; --k) idx[k] = idx[k - 1];
+    idx[k] = i;
+  }
+  for (int i = 0; i < m;) {
+    uint8_t *base = p[idx[i]];
+    int64_t len = bytes[idx[i]];
+    for (++i; i < m && p[idx[i]] == base + len; ++i) len += bytes[idx[i]];
+    if (int st = hip_status(hipMemsetAsync(base, value, (size_t)len, s), "hipMemsetAsync")) return st;
+  }
+  return HIC_OK;
+}
+
+extern "C" int hic_slot_key_range(int n, const hic_slot_job *jobs, int max_len, int32_t *d_minmax, void *stream) {
+  HsJobs J;
+  int64_t max_nrec;
+  if (int e = hs_jobs(n, jobs, max_len, J, max_nrec)) return e;
+  if (!d_minmax) return arg_error("null pointer");
+  hipStream_t s = as_stream(stream);
+  int32_t init[12];
+  for (int i = 0; i < 4 * n; ++i) init[i] = (i & 1) ? -2147483647 - 1 : 2147483647;
+  if (int e = hip_status(hipMemcpyAsync(d_minmax, init, sizeof(int32_t) * 4 * n, hipMemcpyHostToDevice, s),
+                         "hipMemcpyAsync"))
+    return e;
+  const int64_t want = (max_nrec + 7) / 8;
+  const int grid = (int)(want < cu_count() ? want : cu_count());
+  hipLaunchKernelGGL(k_slot_range, dim3(grid, n), dim3(kHT), 0, s, J, d_minmax);
+  return check_launch("k_slot_range");
+}
+
+// key_min / nbins of the 2 n streams into the jobs
+static int hs_tables(HsJobs &J, const int32_t *key_min, const int32_t *nbins) {
+  if (!key_min || !nbins) return arg_error("null pointer");
+  for (int i = 0; i < 2 * J.n; ++i) {
+    if (nbins[i] < 1 || nbins[i] > (1 << 24)) return arg_error("stream %d: nbins", i);
+    J.j[i / 2].key_min[i & 1] = key_min[i];
+    J.j[i / 2].nbins[i & 1] = nbins[i];
+  }
+  return HIC_OK;
+}
+
+extern "C" int hic_slot_key_histogram(int n, const hic_slot_job *jobs, int max_len, const int32_t *key_min,
+                                      const int32_t *nbins, uint32_t *d_counts, uint32_t *d_first,
+                                      const int64_t *bin_offsets, void *stream) {
+  HsJobs J;
+  int64_t max_nrec;
+  if (int e = hs_jobs(n, jobs, max_len, J, max_nrec)) return e;
+  if (int e = hs_tables(J, key_min, nbins)) return e;
+  if (!d_counts || !d_first || !bin_offsets) return arg_error("null pointer");
+  uint8_t *pc[6], *pf[6];
+  int64_t bytes[6];
+  for (int i = 0; i < 2 * n; ++i) {
+    if (bin_offsets[i] < 0) return arg_error("stream %d: bin offset", i);
+    J.j[i / 2].cnt[i & 1] = d_counts + bin_offsets[i];
+    J.j[i / 2].first[i & 1] = d_first + bin_offsets[i];
+    pc[i] = reinterpret_cast<uint8_t *>(d_counts + bin_offsets[i]);
+    pf[i] = reinterpret_cast<uint8_t *>(d_first + bin_offsets[i]);
+    bytes[i] = (int64_t)nbins[i] * 4;
+  }
+  hipStream_t s = as_stream(stream);
+  if (int e = memset_regions(2 * n, pc, bytes, 0, s)) return e;
+  if (int e = memset_regions(2 * n, pf, bytes, 0xFF, s)) return e;
+  const int64_t want = (max_nrec + 7) / 8;
+  const int grid = (int)(want < cu_count() ? want : cu_count());
+  // per-workgroup bins of the channels that fit the LDS, in one stream-ordered scratch
+  int64_t words = 0, max_nbt = 0;
+  for (int k = 0; k < n; ++k) {
+    const int64_t nbt = (int64_t)J.j[k].nbins[0] + J.j[k].nbins[1];
+    if (nbt > kHistLds) continue;
+    words += (int64_t)grid * 2 * nbt;
+    max_nbt = nbt > max_nbt ? nbt : max_nbt;
+  }
+  void *part = nullptr;
+  if (words) {
+    if (int e = hip_status(hipMallocAsync(&part, (size_t)words * 4, s), "hipMallocAsync")) return e;
+    uint32_t *p = static_cast<uint32_t *>(part);
+    for (int k = 0; k < n; ++k) {
+      const int64_t nbt = (int64_t)J.j[k].nbins[0] + J.j[k].nbins[1];
+      if (nbt > kHistLds) continue;
+      J.j[k].part = p;
+      p += (int64_t)grid * 2 * nbt;
+    }
+  }
+  hipLaunchKernelGGL(k_slot_hist, dim3(grid, n), dim3(kHT), 0, s, J);
+  if (int e = check_launch("k_slot_hist")) return e;
+  if (!words) return HIC_OK;
+  hipLaunchKernelGGL(k_slot_hist_reduce, dim3((unsigned)((max_nbt + kHT - 1) / kHT), n), dim3(kHT), 0, s, J, grid);
+  if (int e = check_launch("k_slot_hist_reduce")) return e;
+  return hip_status(hipFreeAsync(part, s), "hipFreeAsync");
+}
+
+extern "C" size_t hic_slot_huffman_pack_workspace_bytes(int n, const hic_slot_job *jobs) {
+  int64_t words = 8;
+  for (int k = 0; jobs && k < n && k < 3; ++k)
+    words += 2 * slot_nrec(jobs[k].nblk > 0 ? jobs[k].nblk : 1, jobs[k].records_per_tile == 2 ? 2 : 1);
+  return (size_t)words * sizeof(int64_t);
+}
+
+extern "C" int hic_slot_huffman_pack(int n, const hic_slot_job *jobs, int max_len, const int32_t *key_min,
+                                     const int32_t *nbins, const uint64_t *const *h_code_bits,
+                                     const uint8_t *const *h_code_len, uint8_t *const *h_out,
+                                     const int64_t *out_bytes, int64_t *d_nbits, void *workspace, void *stream) {
+  HsJobs J;
+  int64_t max_nrec;
+  if (int e = hs_jobs(n, jobs, max_len, J, max_nrec)) return e;
+  if (int e = hs_tables(J, key_min, nbins)) return e;
+  if (!h_code_bits || !h_code_len || !h_out || !out_bytes || !d_nbits || !workspace) return arg_error("null pointer");
+  int64_t *ws = static_cast<int64_t *>(workspace);
+  for (int i = 0; i < 2 * n; ++i) {
+    if (!h_code_bits[i] || !h_code_len[i] || !h_out[i]) return arg_error("stream %d: null pointer", i);
+    if (reinterpret_cast<uintptr_t>(h_out[i]) % 4 || out_bytes[i] % 4 || out_bytes[i] <= 0)
+      return arg_error("stream %d: out must be 4-byte aligned and sized", i);
+    HsJob &j = J.j[i / 2];
+    j.cbits[i & 1] = h_code_bits[i];
+    j.clen[i & 1] = h_code_len[i];
+    j.out[i & 1] = reinterpret_cast<uint32_t *>(h_out[i]);
+    j.out_words[i & 1] = out_bytes[i] / 4;
+    j.bits[i & 1] = ws;
+    ws += j.nrec;
+    j.d_nbits = d_nbits + (i & ~1);
+  }
+  hipStream_t s = as_stream(stream);
+  if (int e = memset_regions(2 * n, h_out, out_bytes, 0, s)) return e;
+  hipLaunchKernelGGL(k_slot_pack_sizes, dim3((unsigned)max_nrec, n), dim3(kHT), 0, s, J);
+  hipLaunchKernelGGL(k_slot_pack_scan, dim3(2, n), dim3(kHT), 0, s, J);
+  hipLaunchKernelGGL(k_slot_pack_bits, dim3((unsigned)max_nrec, n), dim3(kHT), kPackWords * sizeof(uint32_t), s, J);
+  const int64_t batches = (max_nrec + kHT - 1) / kHT;
+  const int fgrid = (int)(batches * 8 < cu_count() ? batches * 8 : cu_count());
+  hipLaunchKernelGGL(k_slot_pack_fill, dim3(fgrid, n), dim3(kHT), 0, s, J);
+  return check_launch("k_slot_pack_fill");
 }

@@ -650,7 +650,7 @@ __global__ __launch_bounds__(kScan16T) void k_rle_scan16b(RleJobs16 jobs, uint32
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t nt = J.nrec, np = (nt + kScan16T - 1) / kScan16T;
   const int64_t *tiles = J.ws;
-  int64_t *offs = J.ws + 3 * nt;
+  int64_t *offs = J.ws + rle_offs_word(nt);
   uint64_t *gran = reinterpret_cast<uint64_t *>(J.ws + 5 * nt);  // 3 per partition
   const uint32_t tag = (epoch << 2) | 1u;
   const int64_t t = p * kScan16T + threadIdx.x;
@@ -824,7 +824,7 @@ __global__ __launch_bounds__(256) void k_rle_emit16b(RleJobs16 jobs) {
       }
     }
     // the tile's first record (a 64-block tile may carry two 32-block records)
-    const int64_t *offs = J.ws + 3 * J.nrec;
+    const int64_t *offs = J.ws + rle_offs_word(J.nrec);
     n.off = offs[r0 * 2 + 0];
     n.prev = offs[r0 * 2 + 1];
     n.pdc = (lane == 0 && b > 0 && b <= J.nblk) ? (int)J.blocks[(b - 1) * 64] : 0;
@@ -910,7 +910,7 @@ __global__ __launch_bounds__(256) void k_rle_slots_compact(RleJobs16 jobs) {
     while (k + 1 < jobs.n && g >= jobs.j[k + 1].tile0) ++k;
     const RleJob16 &J = jobs.j[k];
     const int64_t r = g - J.tile0, capr = 63 * J.bpr;
-    const int64_t off = J.ws[3 * J.nrec + 2 * r];
+    const int64_t off = J.ws[rle_offs_word(J.nrec) + 2 * r];
     const int4 ix = *reinterpret_cast<const int4 *>(J.sidx + 4 * r);
     const int n = ix.x, nf = ix.w;
     for (int64_t i = lane; i < nf; i += 64)
@@ -1797,7 +1797,7 @@ extern "C" int hic_rle_tile_index_i16(const int16_t *blocks, int64_t nblk, int r
   if (nblk <= 0) return arg_error("nblk");
   if (records_per_tile != 1 && records_per_tile != 2) return arg_error("records_per_tile must be 1 or 2");
   const int64_t ntiles = (nblk + kWT - 1) / kWT, nrec = (nblk * records_per_tile + kWT - 1) / kWT;
-  const int64_t *offs = static_cast<const int64_t *>(workspace) + 3 * nrec;
+  const int64_t *offs = static_cast<const int64_t *>(workspace) + rle_offs_word(nrec);
   hipLaunchKernelGGL(k_rle_index16, dim3((unsigned)((ntiles + 255) / 256)), dim3(256), 0, as_stream(stream), offs,
                      records_per_tile == 2 ? 1 : 0, ntiles, blocks, d_index);
   return check_launch("k_rle_index16");

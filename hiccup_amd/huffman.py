@@ -579,42 +579,88 @@ def _fan_out(calls, stream=None):
         cur.wait_stream(st)
 
 
+class SlotStream:
+    """One key stream of a slot-layout encoder's channel, read where the fused encoder
+    left it (csrc/slots.h; no compaction): job = the channel's _lib.SlotJob after
+    hic_rle_slots_close, n = its symbol count, which = 0 the symbol lengths, 1 the
+    values.  For DeviceStreams, in place of a contiguous (tensor, n)."""
+
+    def __init__(self, job, n, which):
+        self.job, self.n, self.which = job, int(n), int(which)
+
+
 class DeviceStreams:
     """Several device key streams at once (the nine of codec.jpeg_encode): the same
     trees and packed bits as one DeviceStream each, with the host round trips
     batched -- one copy back for all key ranges, one for all histograms, one upload
     of all code tables, one copy back for every stream's bits -- instead of five
-    synchronising copies per stream."""
+    synchronising copies per stream.  A stream is a contiguous (tensor, n) or a
+    SlotStream; the slot streams of up to three channels (each channel's lengths and
+    values together) go through the hic_slot_* entry points, one launch per phase
+    for all of them."""
 
     def __init__(self, keys_list, stream=None):
         """stream: the stream the keys were produced on (None: the current one); every
         launch, allocation and host read here runs on it."""
-        self.keys = [k for k, _ in keys_list]
-        self.n = [int(n) for _, n in keys_list]
+        slot = [(i, it) for i, it in enumerate(keys_list) if isinstance(it, SlotStream)]
+        self.keys = [None if isinstance(it, SlotStream) else it[0] for it in keys_list]
+        self.n = [it.n if isinstance(it, SlotStream) else int(it[1]) for it in keys_list]
         self.stream = stream
         if min(self.n) == 0:
             raise ValueError("empty key stream")
+        # slot streams: the channels' jobs and, per (channel, which), the stream's index
+        self._sjobs, self._srow = None, []
+        if slot:
+            chans = []
+            for _, it in slot:
+                if it.job.slot_len not in [j.slot_len for j in chans]:
+                    chans.append(it.job)
+            if len(chans) > 3:
+                raise ValueError("at most three slot channels")
+            self._srow = [None] * (2 * len(chans))
+            for i, it in slot:
+                self._srow[2 * [j.slot_len for j in chans].index(it.job.slot_len) + it.which] = i
+            if None in self._srow:
+                raise ValueError("a slot channel's lengths and values are coded together: pass both")
+            self._sjobs = (_lib.SlotJob * len(chans))(*chans)
         with device.on_stream(stream):
             self._histograms()
+
+    def _contiguous(self):
+        return [(i, k, n) for i, (k, n) in enumerate(zip(self.keys, self.n)) if k is not None]
 
     def _histograms(self):
         stream = self.stream
         lib = _lib.load()
         s = device.stream_ptr(stream)
         m = len(self.keys)
-        mm = device.empty((m, 2), torch.int32)
-        for i, (k, n) in enumerate(zip(self.keys, self.n)):
+        nj = len(self._srow) // 2
+        # rows 0 .. m - 1: the contiguous streams in place; then the slot channels' 2 nj
+        mm = device.empty((m + 2 * nj, 2), torch.int32)
+        for i, k, n in self._contiguous():
             _lib.call("hic_key_range", device.ptr(k), k.element_size(), n, device.ptr(mm[i]), s)
+        if nj:
+            _lib.call("hic_slot_key_range", nj, self._sjobs, 15, device.ptr(mm[m]), s)
         rng = mm.cpu().numpy()
+        for r, i in enumerate(self._srow):
+            rng[i] = rng[m + r]
+        rng = rng[:m]
         self.lo = [int(a) for a, _ in rng]
         self.nbins = [int(b) - int(a) + 1 for a, b in rng]
         off = np.concatenate([[0], np.cumsum(self.nbins)]).astype(np.int64)
         counts = device.empty((int(off[-1]),), torch.int32)
         first = device.empty((int(off[-1]),), torch.int32)
-        _fan_out([lambda sp, i=i, k=k, n=n: _lib.call(
+        calls = [lambda sp, i=i, k=k, n=n: _lib.call(
             "hic_key_histogram", device.ptr(k), k.element_size(), n, self.lo[i], self.nbins[i],
             ctypes.c_void_p(counts.data_ptr() + 4 * int(off[i])), ctypes.c_void_p(first.data_ptr() + 4 * int(off[i])),
-            sp) for i, (k, n) in enumerate(zip(self.keys, self.n))], stream)
+            sp) for i, k, n in self._contiguous()]
+        if nj:
+            i32 = lambda v: (ctypes.c_int32 * len(v))(*v)  # noqa: E731
+            calls.append(lambda sp: _lib.call(
+                "hic_slot_key_histogram", nj, self._sjobs, 15, i32([self.lo[i] for i in self._srow]),
+                i32([self.nbins[i] for i in self._srow]), device.ptr(counts), device.ptr(first),
+                (ctypes.c_int64 * (2 * nj))(*[int(off[i]) for i in self._srow]), sp))
+        _fan_out(calls, stream)
         c_all = counts.cpu().numpy().view(np.uint32)
         f_all = first.cpu().numpy().view(np.uint32)
         self.counts, self.trees = [], []
@@ -650,19 +696,33 @@ class DeviceStreams:
         cb = device.to_device(np.concatenate([b for b, _ in tabs]).view(np.int64))
         cl = device.to_device(np.concatenate([l for _, l in tabs]))
         out = device.empty((int(boff[-1]),), torch.uint8)
-        nbits = device.empty((m,), torch.int64)
+        # bit counts: the streams' in place, then the slot channels' block of 2 per channel
+        nbits = device.empty((m + len(self._srow),), torch.int64)
         # one workspace per side stream: the launches of one stream run in order
-        wss = [device.workspace(self._lib.hic_huffman_pack_workspace_bytes(max(self.n))) for _ in range(_FAN)]
-        _fan_out([lambda sp, i=i, k=k, n=n: _lib.call(
+        cont = self._contiguous()
+        wss = [device.workspace(self._lib.hic_huffman_pack_workspace_bytes(max(n for _, _, n in cont)))
+               for _ in range(_FAN if cont else 0)]
+        calls = [lambda sp, j=j, i=i, k=k, n=n: _lib.call(
             "hic_huffman_pack", device.ptr(k), k.element_size(), n, self.lo[i], self.nbins[i],
             ctypes.c_void_p(cb.data_ptr() + 8 * int(toff[i])), ctypes.c_void_p(cl.data_ptr() + int(toff[i])),
             ctypes.c_void_p(out.data_ptr() + int(boff[i])), nbytes[i], ctypes.c_void_p(nbits.data_ptr() + 8 * i),
-            device.ptr(wss[i % _FAN]), sp) for i, (k, n) in enumerate(zip(self.keys, self.n))], self.stream)
+            device.ptr(wss[j % _FAN]), sp) for j, (i, k, n) in enumerate(cont)]
+        if self._srow:
+            nj, rows = len(self._srow) // 2, self._srow
+            sws = device.workspace(self._lib.hic_slot_huffman_pack_workspace_bytes(nj, self._sjobs))
+            ptrs = lambda base, step, offs: (ctypes.c_void_p * len(rows))(  # noqa: E731
+                *[base + step * int(offs[i]) for i in rows])
+            calls.append(lambda sp: _lib.call(
+                "hic_slot_huffman_pack", nj, self._sjobs, 15, (ctypes.c_int32 * len(rows))(*[self.lo[i] for i in rows]),
+                (ctypes.c_int32 * len(rows))(*[self.nbins[i] for i in rows]), ptrs(cb.data_ptr(), 8, toff),
+                ptrs(cl.data_ptr(), 1, toff), ptrs(out.data_ptr(), 1, boff),
+                (ctypes.c_int64 * len(rows))(*[nbytes[i] for i in rows]), device.ptr(nbits[m:]), device.ptr(sws), sp))
+        _fan_out(calls, self.stream)
         # the bits (~40 MB at 8K) and the bit counts copied back without waiting:
         # into a pinned pool buffer, on the stream after the packing
         cur = self.stream if self.stream is not None else torch.cuda.current_stream()
         host = device.host_empty((out.numel(),), np.uint8)
-        nb_host = torch.empty((m,), dtype=torch.int64, pin_memory=True)
+        nb_host = torch.empty((nbits.numel(),), dtype=torch.int64, pin_memory=True)
         with torch.cuda.stream(cur):
             nb_host.copy_(nbits, non_blocking=True)
             if device._is_pinned(host):
@@ -674,6 +734,8 @@ class DeviceStreams:
             done.synchronize()
             h = host if device._is_pinned(host) else device.to_host(out)
             nb = nb_host.numpy()
+            for r, i in enumerate(self._srow):
+                nb[i] = nb[m + r]
             res = []
             for i in range(m):
                 if int(nb[i]) != totals[i]:

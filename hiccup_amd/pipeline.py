@@ -348,28 +348,35 @@ class Encoder:
                                     self.ws_bytes[k], ix)
         return jobs
 
-    def hic_image(self, stream=None):
+    def hic_image(self, stream=None, from_slots=False):
         """codec.jpeg_encode of this encode, from the device streams: the nine Huffman
         trees from GPU key histograms, the nine bit strings packed on the GPU
         (huffman.DeviceStreams); == codec.jpeg_encode(the encoded CompressedImage)
-        for an unsharded encoder (syncs)."""
-        from . import hicimage as hic
-        from . import huffman
+        for an unsharded encoder (syncs).  A slot-layout encoder compacts its stream
+        first (sym_len / sym_val are valid afterwards); with from_slots=True the six AC
+        streams are histogrammed and packed straight from the slots instead
+        (huffman.SlotStream: no compaction, sym_len / sym_val hold only the EOB the
+        close wrote).  from_slots changes nothing for the coefficient chain."""
         if self.rows != (0, self.H):
             raise ValueError("hic_image needs the whole image (an unsharded encoder)")
-        self.compact(stream)
+        from_slots = bool(from_slots) and self.slots
+        if not from_slots:
+            self.compact(stream)
         with device.on_stream(stream):  # the counts and histograms are read after the stream's kernels
-            return self._hic_image(stream)
+            return self._hic_image(stream, from_slots)
 
-    def _hic_image(self, stream):
+    def _hic_image(self, stream, from_slots):
         from . import hicimage as hic
         from . import huffman
         counts = self.counts.cpu().tolist()
+        jobs = self._slot_jobs() if from_slots else None
         keys = {}
         for i, k in enumerate(CHANNELS):
             check_count(int(counts[i]), k)
             c = int(counts[i])
-            keys[k] = ((self.dc[k], self.dc[k].numel()), (self.sym_val[k], c), (self.sym_len[k], c))
+            dc = (self.dc[k], self.dc[k].numel())
+            keys[k] = ((dc, huffman.SlotStream(jobs[i], c, 1), huffman.SlotStream(jobs[i], c, 0)) if from_slots else
+                       (dc, (self.sym_val[k], c), (self.sym_len[k], c)))
         # the nine streams in payload order, their host round trips batched
         order = [(k, j) for j in range(3) for k in CHANNELS]
         ds = huffman.DeviceStreams([keys[k][j] for k, j in order], stream=stream)

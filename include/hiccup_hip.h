@@ -242,6 +242,32 @@ int hic_encode420_slots_u8(const uint8_t *rgb, int64_t H, int64_t W, const hic_s
                            void *stream, void *ev_start, void *ev_stop);
 int hic_rle_slots_close(int n, const hic_slot_job *jobs, int max_len, void *stream);
 int hic_rle_slots_compact(int n, const hic_slot_job *jobs, int max_len, void *stream);
+/* The Huffman stage's key range, histogram and bit packing (hic_key_range /
+ * hic_key_histogram / hic_huffman_pack below) read straight from the slot layout,
+ * after hic_rle_slots_close and with no hic_rle_slots_compact: results are exactly
+ * those of the contiguous entry points on the compacted stream.  Channel k of the n
+ * (1..3) jobs gives streams 2k (its symbol lengths, 1-byte keys) and 2k + 1 (its
+ * values, 2-byte keys); the fillers before each record and the EOB belong to both.
+ * Every job is checked before any device call (HIC_ERR_ARG; max_len must be 15).
+ *  hic_slot_key_range: d_minmax (device int32[4n]) = {min, max} per stream.
+ *  hic_slot_key_histogram: key_min / nbins / bin_offsets are host arrays of 2n; stream
+ *    i's bins are d_counts / d_first + bin_offsets[i] (uint32 entries): the count and
+ *    the position in the channel's stream of the key's first appearance (0xFFFFFFFF:
+ *    absent) -- a filler run counts nfill_r times at its record's stream offset.  A
+ *    channel's stream stays below 2^32 symbols by the job's nblk limit.
+ *  hic_slot_huffman_pack: h_code_bits / h_code_len / h_out are host arrays of 2n
+ *    device pointers (tables as hic_huffman_pack's, indexed key - key_min[i]; h_out[i]
+ *    4-byte aligned, out_bytes[i] a multiple of 4, zeroed here), d_nbits device
+ *    int64[2n] = each stream's bits; workspace >= hic_slot_huffman_pack_workspace_bytes. */
+int hic_slot_key_range(int n, const hic_slot_job *jobs, int max_len, int32_t *d_minmax, void *stream);
+int hic_slot_key_histogram(int n, const hic_slot_job *jobs, int max_len, const int32_t *key_min,
+                           const int32_t *nbins, uint32_t *d_counts, uint32_t *d_first, const int64_t *bin_offsets,
+                           void *stream);
+size_t hic_slot_huffman_pack_workspace_bytes(int n, const hic_slot_job *jobs);
+int hic_slot_huffman_pack(int n, const hic_slot_job *jobs, int max_len, const int32_t *key_min,
+                          const int32_t *nbins, const uint64_t *const *h_code_bits,
+                          const uint8_t *const *h_code_len, uint8_t *const *h_out, const int64_t *out_bytes,
+                          int64_t *d_nbits, void *workspace, void *stream);
 int hic_rle_decode_i16_slots(const uint8_t *slot_len, const int16_t *slot_val, const int64_t *d_nsym,
                              const int32_t *dc_diff, int64_t nblk, int records_per_tile, const int32_t *d_index,
                              int16_t *blocks, int64_t *d_status, void *stream);
