@@ -9,7 +9,8 @@ namespace hic {
 static thread_local char g_last_error[512] = "";
 
 // hic_set_knob values (-1 = default; read by the launchers on every call)
-static int g_knobs[HIC_KNOB_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
+static int g_knobs[HIC_KNOB_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
+static_assert(HIC_KNOB_COUNT == 17, "one -1 per knob");
 int knob(int k) {
   const int v = g_knobs[k];
   if (v >= 0) return v;
@@ -18,6 +19,7 @@ int knob(int k) {
     case HIC_KNOB_COLOR_SEG: return 8;
     case HIC_KNOB_RLE_NT: return 1;
     case HIC_KNOB_ENCODE_ORDER: return 6;  // XCD-major workgroups, odd unit rows bottom-up
+    case HIC_KNOB_ENCODE_BAND: return 1;   // workgroups of four stacked units (halo rows through LDS)
     default: return k == HIC_KNOB_DCT_WAVES_PER_CU ? -1 : 0;
   }
 }
@@ -96,6 +98,7 @@ extern "C" int hic_set_knob(int k, int value) {
   }
   if (k == HIC_KNOB_ENCODE_ORDER && value != -1 && (value < 0 || value > 7 || (value & 1)))
     return hic::arg_error("encode_order 0, 2, 4 or 6");
+  if (k == HIC_KNOB_ENCODE_BAND && (value < -1 || value > 1)) return hic::arg_error("encode_band 0 or 1");
   if (value < -1) return hic::arg_error("knob value %d", value);
 #ifndef HIC_DEV
   if (k == HIC_KNOB_DEV && value > 0) return hic::arg_error("the dev knob needs a -DHIC_DEV build");

@@ -18,16 +18,23 @@
 // its lanes past W compute on whatever the loads return and store nothing, the
 // right-border pixel goes to its last lane); its block rows then straddle RLE
 // tiles, so the tile records come from a tile pass after the launch.  One wave
-// per unit:
-//   1. colour: 19 RGB rows (the 16 rows + the 2 + 1 rows of pyrDown's vertical
-//      taps), 24 B per lane per row (1.5 KiB contiguous per wave-row, buffer loads
+// per unit; the four waves of a workgroup are four vertically adjacent units of one
+// strip (a band; knob encode_band 1, the default) and share pyrDown's halo rows:
+//   1. colour: the unit's 16 RGB rows and the 2 + 1 rows above / below of pyrDown's
+//      vertical taps.  Inside a band a halo row is a neighbour wave's own row: that
+//      wave converts it and passes its horizontal pyrDown sums (16 B per lane) through
+//      LDS, in the DCT stage, idle until then (one workgroup barrier; EncColour::
+//      band_edges / band_rows).  Only a band's first and last unit convert halo rows
+//      themselves: 67 rows per 64 instead of 76.  (With encode_band 0, and in
+//      k_encode420_batch, every wave loads and converts all 19 rows: rows().)
+//      24 B per lane per row (1.5 KiB contiguous per wave-row, buffer loads
 //      at a scalar row offset); YCC by v_dot4 (ycc8); Y of rows 0..15 stays in
 //      registers (two 8x8 blocks per lane); Cr / Cb per pixel, the horizontal
 //      [1 4 6 4 1] at even columns with the neighbour pixels by DPP wave shifts
 //      (the strip's edge pixels converted once per unit, one row per lane, and
 //      written into lane 0 / 63 by v_writelane), the vertical taps over a 5-row
 //      window -> 8 chroma rows x 4 columns per lane and plane;
-//   2. DCT of Y block row 0 and row 1 (lane = block; after all 19 colour rows):
+//   2. DCT of Y block row 0 and row 1 (lane = block; after all colour rows):
 //      coefficients to the LDS stage at their zig-zag slot, copied out in 1 KiB
 //      stores, the tile record from the stage;
 //   3. chroma: the colour stage left the chroma rows in a 4 KiB LDS area per wave;
@@ -37,11 +44,12 @@
 //      half-tile records (hic_rle_job16.records_per_tile = 2).
 // Exact-tie fallbacks (dct_block_2ph, dct_fix26) run in place on the pixels still
 // in registers: a unit never revisits HBM.
-// RGB traffic: 19/16 of the image fetched by the waves (the vertical halo rows are
-// re-read by the unit above / below), of which the default unit order (knob
-// encode_order 6: XCD-major workgroups, odd unit rows bottom-up) has the L2 serve
-// most re-reads: 109.6 MB from HBM per 8K launch against the image's 99.5 MB;
-// coefficient writes 3 B per pixel.
+// RGB traffic: 67/64 of the image fetched by the waves in bands (only a band's outer
+// halo rows are re-read), 19/16 with one unit per wave (knob encode_band 0, in the
+// order of knob encode_order 6: XCD-major workgroups, odd unit rows bottom-up, where
+// the L2 serves most re-reads).  From HBM per 8K launch of the slot kernel: 114.2 MB
+// in bands, 115.2 MB without, against the image's 99.5 MB
+// (profiles/r08/halo_xchg/); coefficient writes 3 B per pixel.
 #include "color_core.h"
 #include "dct_core.h"
 #include "rle_core.h"
@@ -299,7 +307,9 @@ struct EncColour {
     ring_b[t % (kLA + 1)] = __builtin_amdgcn_raw_buffer_load_b64(rsrc, voff + 16, so, HIC_ENC_LOAD_AUX);
   }
 
-  __device__ __forceinline__ void init(const Enc420 &E, int y0, int s, int lane_, int nb, bool rev = false) {
+  // preload: the first kLA rows of the pass (rows()) loaded here
+  __device__ __forceinline__ void init(const Enc420 &E, int y0, int s, int lane_, int nb, bool rev = false,
+                                       bool preload = true) {
     lane = lane_;
     rlane = __builtin_amdgcn_readfirstlane(nb - 1);
     const int W = E.W, H = E.H, pitch = 3 * W;
@@ -341,8 +351,35 @@ struct EncColour {
     k6 = opq(0x00060006u);
     k128 = opq(0x00800080u);
     // rev: the rows run bottom-up (rows_rev)
+    if (preload) {
 #pragma unroll
-    for (int t = 0; t < kLA; ++t) load_row_at(rev ? NR - 1 - t : t, t);
+      for (int t = 0; t < kLA; ++t) load_row_at(rev ? NR - 1 - t : t, t);
+    }
+  }
+
+  // horizontal pyrDown sums of input row r (its packed chroma pixels c) -> hr
+  __device__ __forceinline__ void hsums(int r, const uint32_t (&c)[8], uint32_t (&hr)[4]) {
+    // neighbour pixels x0 - 2, x0 - 1 (left lane) and x0 + 8 (right lane)
+    const uint32_t l2 = set_lane<0>(wshr1(c[6]), __builtin_amdgcn_readlane((int)hal_l2, r));
+    const uint32_t l1 = set_lane<0>(wshr1(c[7]), __builtin_amdgcn_readlane((int)hal_l1, r));
+    const uint32_t r0 = set_lane_s(wshl1(c[0]), __builtin_amdgcn_readlane((int)hal_r, r), lane, rlane);
+    hr[0] = pk_taps5(l2, l1, c[0], c[1], c[2], k4, k6);
+    hr[1] = pk_taps5(c[0], c[1], c[2], c[3], c[4], k4, k6);
+    hr[2] = pk_taps5(c[2], c[3], c[4], c[5], c[6], k4, k6);
+    hr[3] = pk_taps5(c[4], c[5], c[6], c[7], r0, k4, k6);
+  }
+
+  // chroma row i of the unit from the five h rows a .. a + 4 -> the LDS chroma area
+  __device__ __forceinline__ void chroma_row(int a, int i, uint32_t *s_chroma) {
+    uint32_t v[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)  // sum + 128 < 2^16: (sum + 128) >> 8 is the high byte
+      v[j] = pk_add16(pk_taps5(h[a][j], h[a + 1][j], h[a + 2][j], h[a + 3][j], h[a + 4][j], k4, k6), k128);
+    // high bytes: x01 = (cr0, cr1, cb0, cb1), x23 = (cr2, cr3, cb2, cb3)
+    const uint32_t x01 = __builtin_amdgcn_perm(v[1], v[0], 0x07030501u);
+    const uint32_t x23 = __builtin_amdgcn_perm(v[3], v[2], 0x07030501u);
+    s_chroma[(i & 7) * 64 + lane] = __builtin_amdgcn_perm(x23, x01, 0x05040100u);
+    s_chroma[512 + (i & 7) * 64 + lane] = __builtin_amdgcn_perm(x23, x01, 0x07060302u);
   }
 
   // all NR input rows, top-down, or bottom-up (rev, wave-uniform; init(.., rev)): a
@@ -376,30 +413,136 @@ struct EncColour {
         q = rev ? yv : q;
         if constexpr (PIN_Y) asm volatile("" : "+v"(q.x), "+v"(q.y));
       }
-      // neighbour pixels x0 - 2, x0 - 1 (left lane) and x0 + 8 (right lane)
-      const uint32_t l2 = set_lane<0>(wshr1(c[6]), __builtin_amdgcn_readlane((int)hal_l2, r));
-      const uint32_t l1 = set_lane<0>(wshr1(c[7]), __builtin_amdgcn_readlane((int)hal_l1, r));
-      const uint32_t r0 = set_lane_s(wshl1(c[0]), __builtin_amdgcn_readlane((int)hal_r, r), lane, rlane);
-      h[t][0] = pk_taps5(l2, l1, c[0], c[1], c[2], k4, k6);
-      h[t][1] = pk_taps5(c[0], c[1], c[2], c[3], c[4], k4, k6);
-      h[t][2] = pk_taps5(c[2], c[3], c[4], c[5], c[6], k4, k6);
-      h[t][3] = pk_taps5(c[4], c[5], c[6], c[7], r0, k4, k6);
+      hsums(r, c, h[t]);
       // chroma row i has all five input rows 2 i .. 2 i + 4: the turns t - 4 .. t
       // (t even; i = t / 2 - 2, or bottom-up (NR - 1 - t) / 2)
-      if (t >= 4 && t % 2 == 0) {
-        const int a = t - 4, i = rev ? (NR - 1 - t) / 2 : t / 2 - 2;  // NR odd
-        uint32_t v[4];
+      if (t >= 4 && t % 2 == 0) chroma_row(t - 4, rev ? (NR - 1 - t) / 2 : t / 2 - 2, s_chroma);  // NR odd
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+
+  // ---- stacked bands (knob encode_band 1; NR = 19) ----
+  // A workgroup's waves are vertically adjacent units of one strip.  The three halo
+  // rows two of them share are converted once, by the wave that owns them, and their
+  // horizontal sums h reach the neighbour through LDS: each wave has an exchange area
+  // (its DCT stage, idle during the colour stage) of six row slots of 64 x 16 B, one
+  // per input row 0, 1 (above), 2, 16, 17 (own rows 0, 14, 15) and 18 (below).
+  static constexpr int kAreaU4 = 64 * kStageU2 / 2;  // a wave's stage, in uint4
+  static constexpr int slot_of(int r) { return r < 3 ? r : r - 13; }
+  __device__ __forceinline__ void xput(uint4 *area, int r, const uint32_t (&hr)[4]) {
+    area[slot_of(r) * 64 + lane] = make_uint4(hr[0], hr[1], hr[2], hr[3]);
+  }
+  __device__ __forceinline__ void xget(const uint4 *area, int r) {
+    const uint4 v = area[slot_of(r) * 64 + lane];
+    h[r][0] = v.x; h[r][1] = v.y; h[r][2] = v.z; h[r][3] = v.w;
+  }
+  // input row r's words -> its packed Y row and h sums
+  __device__ __forceinline__ uint2 convert(int r, u32x4 qa, u32x2 qb, uint32_t (&hr)[4]) {
+    const uint32_t wd[6] = {qa.x, qa.y, qa.z, qa.w, qb.x, qb.y};
+    uint32_t Yh[8], c[8];
+    ycc8(wd, K, Yh, c);
+    hsums(r, c, hr);
+    return make_uint2(ypack4(Yh, 0), ypack4(Yh, 4));
+  }
+  // the loads of the edge phase: the unit's rows 2, 16, 17, the halo rows it has no
+  // neighbour for (wave-uniform: no wave above / below in the workgroup), and the
+  // first kLA rows of the interior pass (after init(.., preload = false))
+  __device__ __forceinline__ void edge_loads(u32x4 (&ea)[6], u32x2 (&eb)[6], bool has_up, bool has_dn) {
+    auto ld = [&](int k, int r) {
+      const int so = __builtin_amdgcn_readlane(roff, r);
+      ea[k] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, so, HIC_ENC_LOAD_AUX);
+      eb[k] = __builtin_amdgcn_raw_buffer_load_b64(rsrc, voff + 16, so, HIC_ENC_LOAD_AUX);
+    };
+    ld(0, 2); ld(1, 16); ld(2, 17);
+    if (!has_up) { ld(3, 0); ld(4, 1); }
+    if (!has_dn) ld(5, 18);
 #pragma unroll
-        for (int j = 0; j < 4; ++j)  // sum + 128 < 2^16: (sum + 128) >> 8 is the high byte
-          v[j] = pk_add16(pk_taps5(h[a][j], h[a + 1][j], h[a + 2][j], h[a + 3][j], h[a + 4][j], k4, k6), k128);
-        // high bytes: x01 = (cr0, cr1, cb0, cb1), x23 = (cr2, cr3, cb2, cb3)
-        const uint32_t x01 = __builtin_amdgcn_perm(v[1], v[0], 0x07030501u);
-        const uint32_t x23 = __builtin_amdgcn_perm(v[3], v[2], 0x07030501u);
-        s_chroma[(i & 7) * 64 + lane] = __builtin_amdgcn_perm(x23, x01, 0x05040100u);
-        s_chroma[512 + (i & 7) * 64 + lane] = __builtin_amdgcn_perm(x23, x01, 0x07060302u);
+    for (int t = 0; t < kLA; ++t) load_row_at(3 + t, t);
+  }
+  // Edge phase: the unit's rows 0, 14, 15 (input rows 2, 16, 17) -> yq, their h into
+  // the own slots, rows 16, 17 also into slots 0, 1 of the wave below and row 2 into
+  // slot 18 of the wave above; a wave without that neighbour converts the halo rows
+  // itself (the band's first / last unit row: the image's reflect-101 rows or the
+  // next band's).  A workgroup barrier follows (the caller's).
+  __device__ __forceinline__ void band_edges(uint2 (&yq)[16], uint4 *area, bool has_up, bool has_dn) {
+    u32x4 ea[6];
+    u32x2 eb[6];
+    edge_loads(ea, eb, has_up, has_dn);
+    uint32_t hr[4];
+    auto own = [&](int k, int r) {
+      uint2 &q = yq[r - 2];
+      q = convert(r, ea[k], eb[k], hr);
+      asm volatile("" : "+v"(q.x), "+v"(q.y));
+      xput(area, r, hr);
+    };
+    own(0, 2);
+    if (has_up) xput(area - kAreaU4, 18, hr);
+    own(1, 16);
+    if (has_dn) xput(area + kAreaU4, 0, hr);
+    own(2, 17);
+    if (has_dn) xput(area + kAreaU4, 1, hr);
+    __builtin_amdgcn_sched_barrier(0);
+    if (!has_up) {
+      convert(0, ea[3], eb[3], hr);
+      xput(area, 0, hr);
+      convert(1, ea[4], eb[4], hr);
+      xput(area, 1, hr);
+    }
+    if (!has_dn) {
+      convert(18, ea[5], eb[5], hr);
+      xput(area, 18, hr);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  // Interior pass, after the barrier: input rows 3 .. 15 top-down through the load
+  // ring; the vertical taps take input rows 0, 1, 2 and 16, 17, 18 from the own slots
+  __device__ __forceinline__ void band_rows(uint2 (&yq)[16], uint32_t *s_chroma, const uint4 *area) {
+    xget(area, 0);
+    xget(area, 1);
+    xget(area, 2);
+#pragma unroll
+    for (int t = 0; t < 13; ++t) {
+      const int r = 3 + t;
+      if (t + kLA < 13) load_row_at(r + kLA, t + kLA);
+      if (r == 15) {
+        xget(area, 16);
+        xget(area, 17);
+        xget(area, 18);
+      }
+      uint2 &q = yq[r - 2];
+      q = convert(r, ring_a[t % (kLA + 1)], ring_b[t % (kLA + 1)], h[r]);
+      asm volatile("" : "+v"(q.x), "+v"(q.y));
+      if (r % 2 == 0) chroma_row(r - 4, r / 2 - 2, s_chroma);  // chroma rows 0 .. 5
+      if (r == 15) {
+        chroma_row(12, 6, s_chroma);
+        chroma_row(14, 7, s_chroma);
       }
       __builtin_amdgcn_sched_barrier(0);
     }
+  }
+  // hic_probe_encode420 in band order: the same loads, folded as fold_rows does
+  __device__ __forceinline__ void fold_band(uint2 (&yq)[16], bool has_up, bool has_dn) {
+    u32x4 ea[6];
+    u32x2 eb[6];
+    edge_loads(ea, eb, has_up, has_dn);
+    auto fold = [&](int r, u32x4 qa, u32x2 qb) {
+      yq[r & 15].x ^= qa.x ^ qa.z ^ qb.x;
+      yq[r & 15].y ^= qa.y ^ qa.w ^ qb.y;
+    };
+    fold(2, ea[0], eb[0]);
+    fold(16, ea[1], eb[1]);
+    fold(17, ea[2], eb[2]);
+    if (!has_up) {
+      fold(0, ea[3], eb[3]);
+      fold(1, ea[4], eb[4]);
+    }
+    if (!has_dn) fold(18, ea[5], eb[5]);
+#pragma unroll
+    for (int t = 0; t < 13; ++t) {
+      if (t + kLA < 13) load_row_at(3 + t + kLA, t + kLA);
+      fold(3 + t, ring_a[t % (kLA + 1)], ring_b[t % (kLA + 1)]);
+    }
+    yq[0].x ^= hal_l2 ^ hal_l1 ^ hal_r;
   }
 
   // hic_probe_encode420: the same NR row loads in the same order, no arithmetic --
@@ -428,14 +571,20 @@ struct EncColour {
 // kernel, the float32 / packed-float32 / integer-MFMA transforms (the packed one
 // again in round 5, with proven windows and a cooperative float64 redo: 70.5-74.9
 // vs 55.6-57.7 us, commit ae5c500), cached stores, the one-pass (look-back +
-// emission) variant and vertically stacked units.
+// emission) variant and vertically stacked units that shared nothing (round 4; with
+// the halo rows exchanged through LDS they are the default since round 8: BAND).
 //
 // SLOTS (TMF 15, whole images with W % 512 == 0; hic_encode420_slots_u8): each pass
 // emits its record's AC symbols and DC differences into the slot layout (slots.h)
 // instead of storing the int16 coefficients: no coefficient ever reaches HBM.
 // One unit (wave g of the launch's E): the kernels below map their waves to units.
-template <int TMF, bool SLOTS>
-__device__ __forceinline__ void encode_unit(const Enc420 &E, int g, int lane, uint2 *st2, uint32_t *s_chroma) {
+// BAND: wave wv of a workgroup of vertically stacked units (k_encode420<.., true>):
+// the colour stage shares the halo rows through LDS and holds the workgroup's one
+// barrier, which every wave of the workgroup reaches -- a wave without a unit (g past
+// the last unit row of a short last band) too, and returns after it.
+template <int TMF, bool SLOTS, bool BAND = false>
+__device__ __forceinline__ void encode_unit(const Enc420 &E, int g, int lane, uint2 *st2, uint32_t *s_chroma,
+                                            int wv = 0) {
   static_assert(!SLOTS || TMF == kSlotM, "the slot layout packs 4-bit lengths (max_len 15)");
   int16_t *st = reinterpret_cast<int16_t *>(st2 + lane * kStageU2);
   const int u0 = __builtin_amdgcn_readfirstlane(g / E.nstrips);
@@ -513,14 +662,31 @@ __device__ __forceinline__ void encode_unit(const Enc420 &E, int g, int lane, ui
     __builtin_amdgcn_sched_barrier(0);
   };
   EncColour<19, HIC_ENC_LA3, true> C;
-  const bool rev = E.alt && (u0 & 1);  // wave-uniform
   // the colour stage (its row loads) at issue priority 1 over the SIMD's waves in
   // their DCT / emission passes: kernel 72.6-73.4 vs 73.6-74.3 us, step 0.0728-0.0740
   // vs 0.0742-0.0760 ms in 5 alternating rounds (priority 2 / 3 within that range;
   // profiles/r06/enc_prio/)
   __builtin_amdgcn_s_setprio(1);
-  C.init(E, y0, s, lane, nb, rev);
-  C.rows(yq, s_chroma, rev);
+  if constexpr (BAND) {
+    const int nrows = E.out_rows >> 4;
+    // wave-uniform, and the same for every wave of the workgroup but for wv
+    const bool live = __builtin_amdgcn_readfirstlane(u0 < nrows);
+    const bool has_up = wv > 0, has_dn = wv + 1 < HIC_ENC_WPB && u0 + 1 < nrows;
+    uint4 *area = reinterpret_cast<uint4 *>(st2);
+    if (live) {
+      C.init(E, y0, s, lane, nb, false, false);
+      C.band_edges(yq, area, has_up, has_dn);
+    }
+    // every slot is written before the barrier and read after it, by its owner alone:
+    // the DCT passes, which reuse the area as their stage, need no second barrier
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    if (!live) return;
+    C.band_rows(yq, s_chroma, area);
+  } else {
+    const bool rev = E.alt && (u0 & 1);  // wave-uniform
+    C.init(E, y0, s, lane, nb, rev);
+    C.rows(yq, s_chroma, rev);
+  }
   __builtin_amdgcn_s_setprio(0);
   __builtin_amdgcn_sched_barrier(0);
   y_blocks(0);
@@ -528,16 +694,27 @@ __device__ __forceinline__ void encode_unit(const Enc420 &E, int g, int lane, ui
   c_blocks();
 }
 
-template <int TMF, bool SLOTS = false>
+// wave wv of logical workgroup bx -> its unit g (strip s of unit row u0 = g / nstrips).
+// Row-major: four consecutive units.  BAND: the workgroups are band-major, then strip,
+// and the waves of one are unit rows 4 band .. 4 band + 3 of its strip (g may lie past
+// the last unit row: a short last band)
+template <bool BAND>
+__device__ __forceinline__ int enc_unit_of(const Enc420 &E, int bx, int wv) {
+  if constexpr (!BAND) return __builtin_amdgcn_readfirstlane(bx * HIC_ENC_WPB + wv);
+  const int band = bx / E.nstrips, s = bx - band * E.nstrips;
+  return __builtin_amdgcn_readfirstlane((band * HIC_ENC_WPB + wv) * E.nstrips + s);
+}
+
+template <int TMF, bool SLOTS = false, bool BAND = false>
 __global__ __launch_bounds__(64 * HIC_ENC_WPB) __attribute__((amdgpu_waves_per_eu(3))) void k_encode420(Enc420 E) {
   __shared__ __attribute__((aligned(16))) uint2 s_stage[HIC_ENC_WPB * 64 * kStageU2];
   __shared__ uint32_t s_chroma_all[HIC_ENC_WPB][2 * 8 * 64];
   const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int bx = __builtin_amdgcn_readfirstlane(E.xcd ? xcd_block((int)blockIdx.x, (int)gridDim.x) : (int)blockIdx.x);
-  // wave g: strip s of unit row u0
-  const int g = __builtin_amdgcn_readfirstlane(bx * HIC_ENC_WPB + wv);
-  if (g >= E.nunits) return;  // wave-uniform
-  encode_unit<TMF, SLOTS>(E, g, lane, s_stage + wv * 64 * kStageU2, s_chroma_all[wv]);
+  const int g = enc_unit_of<BAND>(E, bx, wv);
+  if constexpr (!BAND)
+    if (g >= E.nunits) return;  // wave-uniform
+  encode_unit<TMF, SLOTS, BAND>(E, g, lane, s_stage + wv * 64 * kStageU2, s_chroma_all[wv], wv);
 }
 
 // Several encodes in ONE launch (hic_encode420_batch_u8: the row shards of a
@@ -587,14 +764,14 @@ __device__ __forceinline__ void probe_slot_out(const uint2 *st2, int lane, int n
   }
 }
 
-template <bool SLOTS = false>
+template <bool SLOTS = false, bool BAND = false>
 __global__ __launch_bounds__(64 * HIC_ENC_WPB) __attribute__((amdgpu_waves_per_eu(3))) void k_probe_encode420(
     Enc420 E) {
   __shared__ __attribute__((aligned(16))) uint2 s_stage[HIC_ENC_WPB * 64 * kStageU2];
   const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int bx = __builtin_amdgcn_readfirstlane(E.xcd ? xcd_block((int)blockIdx.x, (int)gridDim.x) : (int)blockIdx.x);
-  const int g = __builtin_amdgcn_readfirstlane(bx * HIC_ENC_WPB + wv);
-  if (g >= E.nunits) return;  // wave-uniform
+  const int g = enc_unit_of<BAND>(E, bx, wv);
+  if (g >= E.nunits) return;  // wave-uniform (no barrier in the probe: nothing is exchanged)
   const int u0 = __builtin_amdgcn_readfirstlane(g / E.nstrips), s = __builtin_amdgcn_readfirstlane(g - u0 * E.nstrips);
   const int y0 = E.out_row0 + 16 * u0, nbx = E.W >> 3, nbxc = E.W >> 4;
   uint2 *st2 = s_stage + wv * 64 * kStageU2;
@@ -602,9 +779,14 @@ __global__ __launch_bounds__(64 * HIC_ENC_WPB) __attribute__((amdgpu_waves_per_e
 #pragma unroll
   for (int r = 0; r < 16; ++r) yq[r] = make_uint2(0, 0);
   EncColour<19, HIC_ENC_LA3, true> C;
-  const bool rev = E.alt && (u0 & 1);
-  C.init(E, y0, s, lane, 64, rev);
-  C.fold_rows(yq, rev);
+  if constexpr (BAND) {
+    C.init(E, y0, s, lane, 64, false, false);
+    C.fold_band(yq, wv > 0, wv + 1 < HIC_ENC_WPB && g + E.nstrips < E.nunits);
+  } else {
+    const bool rev = E.alt && (u0 & 1);
+    C.init(E, y0, s, lane, 64, rev);
+    C.fold_rows(yq, rev);
+  }
   for (int p = 0; p < 3; ++p) {  // Y block rows 0 and 1, then Cr | Cb
     uint2 *row = st2 + lane * kStageU2;
 #pragma unroll
@@ -652,6 +834,24 @@ __global__ __launch_bounds__(64 * HIC_ENC_WPB) __attribute__((amdgpu_waves_per_e
 }  // namespace hic
 
 using namespace hic;
+
+// knob encode_order -> E's unit order; returns whether the launch runs stacked bands
+// (knob encode_band, default 1: k_encode420<.., BAND>, one workgroup per band of
+// HIC_ENC_WPB unit rows and strip, the halo rows shared through LDS -- DESIGN.md
+// section 0, round 8; the bottom-up rows of encode_order's bit 2 do not exist there).
+// encode_order's default 6: XCD-major workgroups, odd unit rows bottom-up (FETCH_SIZE
+// 109.6 vs 131.7 MB per 8K launch, kernel 58.0 vs 58.9 us, bench 0.0996 vs 0.1004
+// ms/step median of 10 alternating pairs: profiles/r04/enc_order_xcd)
+static bool enc_order(Enc420 &E) {
+  const int order = knob(HIC_KNOB_ENCODE_ORDER);
+  E.xcd = (order >> 1) & 1;
+  E.alt = (order >> 2) & 1;
+  return knob(HIC_KNOB_ENCODE_BAND) != 0;
+}
+static dim3 enc_grid(const Enc420 &E, bool band) {
+  if (!band) return dim3((unsigned)((E.nunits + HIC_ENC_WPB - 1) / HIC_ENC_WPB));
+  return dim3((unsigned)(((E.out_rows / 16 + HIC_ENC_WPB - 1) / HIC_ENC_WPB) * E.nstrips));
+}
 
 // checks one encode's arguments and fills its kernel argument (no launch)
 static int prep420(const uint8_t *rgb_rows, int64_t in_row0, int64_t in_rows, int64_t H, int64_t W, int64_t out_row0,
@@ -708,12 +908,7 @@ static int prep420(const uint8_t *rgb_rows, int64_t in_row0, int64_t in_rows, in
   E.nunits = E.nstrips * (int)(out_rows / 16);  // waves
   // one wave per unit (no persistent loop: units are the same size, and the
   // hardware's dispatch balances the tail better than a fixed split)
-  // default 6: XCD-major workgroups, odd unit rows bottom-up (FETCH_SIZE 109.6 vs
-  // 131.7 MB per 8K launch, kernel 58.0 vs 58.9 us, bench 0.0996 vs 0.1004 ms/step
-  // median of 10 alternating pairs: profiles/r04/enc_order_xcd)
-  const int order = knob(HIC_KNOB_ENCODE_ORDER);
-  E.xcd = (order >> 1) & 1;
-  E.alt = (order >> 2) & 1;
+  enc_order(E);
   return HIC_OK;
 }
 
@@ -726,7 +921,8 @@ static int encode420(const uint8_t *rgb_rows, int64_t in_row0, int64_t in_rows, 
   if (int e = prep420(rgb_rows, in_row0, in_rows, H, W, out_row0, out_rows, coef_y, coef_cr, coef_cb, ws_y, ws_cr,
                       ws_cb, max_len, seg, wsb_y, wsb_c, E, recs, aligned))
     return e;
-  const dim3 grid((unsigned)((E.nunits + HIC_ENC_WPB - 1) / HIC_ENC_WPB)), block(64 * HIC_ENC_WPB);
+  const bool band = enc_order(E);
+  const dim3 grid = enc_grid(E, band), block(64 * HIC_ENC_WPB);
   hipStream_t s = as_stream(stream);
   hipEvent_t e0 = static_cast<hipEvent_t>(ev_start), e1 = static_cast<hipEvent_t>(ev_stop);
   auto launch = [&](auto kern) {
@@ -736,9 +932,9 @@ static int encode420(const uint8_t *rgb_rows, int64_t in_row0, int64_t in_rows, 
       hipLaunchKernelGGL(kern, grid, block, 0, s, E);
   };
   if (max_len == 15)
-    launch(k_encode420<15>);
+    band ? launch(k_encode420<15, false, true>) : launch(k_encode420<15>);
   else
-    launch(k_encode420<0>);
+    band ? launch(k_encode420<0, false, true>) : launch(k_encode420<0>);
   if (int e = check_launch("k_encode420")) return e;
   if (recs && !aligned) {  // one record per 64-block tile, all three planes (not seg)
     const int64_t ny = (out_rows / 8) * (W / 8), nc = (out_rows / 16) * (W / 16);
@@ -842,16 +1038,17 @@ extern "C" int hic_encode420_slots_u8(const uint8_t *rgb, int64_t H, int64_t W, 
   E.nstrips = (int)(W / 512);
   E.wlast = 512;
   E.nunits = E.nstrips * (int)(H / 16);
-  const int order = knob(HIC_KNOB_ENCODE_ORDER);
-  E.xcd = (order >> 1) & 1;
-  E.alt = (order >> 2) & 1;
-  const dim3 grid((unsigned)((E.nunits + HIC_ENC_WPB - 1) / HIC_ENC_WPB)), block(64 * HIC_ENC_WPB);
+  const bool band = enc_order(E);
+  const dim3 grid = enc_grid(E, band), block(64 * HIC_ENC_WPB);
   const hipStream_t s = as_stream(stream);
   const hipEvent_t e0 = static_cast<hipEvent_t>(ev_start), e1 = static_cast<hipEvent_t>(ev_stop);
-  if (e0 || e1)
-    hipExtLaunchKernelGGL((k_encode420<kSlotM, true>), grid, block, 0, s, e0, e1, 0, E);
-  else
-    hipLaunchKernelGGL((k_encode420<kSlotM, true>), grid, block, 0, s, E);
+  auto launch = [&](auto kern) {
+    if (e0 || e1)
+      hipExtLaunchKernelGGL(kern, grid, block, 0, s, e0, e1, 0, E);
+    else
+      hipLaunchKernelGGL(kern, grid, block, 0, s, E);
+  };
+  band ? launch(k_encode420<kSlotM, true, true>) : launch(k_encode420<kSlotM, true>);
   return check_launch("k_encode420<slots>");
 }
 
@@ -882,16 +1079,17 @@ extern "C" int hic_probe_encode420(const uint8_t *rgb, int64_t H, int64_t W, int
   E.nstrips = (int)(W / 512);
   E.wlast = 512;
   E.nunits = E.nstrips * (int)(H / 16);
-  const int order = knob(HIC_KNOB_ENCODE_ORDER);
-  E.xcd = (order >> 1) & 1;
-  E.alt = (order >> 2) & 1;
-  const dim3 grid((unsigned)((E.nunits + HIC_ENC_WPB - 1) / HIC_ENC_WPB)), block(64 * HIC_ENC_WPB);
+  const bool band = enc_order(E);
+  const dim3 grid = enc_grid(E, band), block(64 * HIC_ENC_WPB);
   const hipStream_t s = as_stream(stream);
   const hipEvent_t e0 = static_cast<hipEvent_t>(ev_start), e1 = static_cast<hipEvent_t>(ev_stop);
-  if (e0 || e1)
-    hipExtLaunchKernelGGL(k_probe_encode420<false>, grid, block, 0, s, e0, e1, 0, E);
-  else
-    hipLaunchKernelGGL(k_probe_encode420<false>, grid, block, 0, s, E);
+  auto launch = [&](auto kern) {
+    if (e0 || e1)
+      hipExtLaunchKernelGGL(kern, grid, block, 0, s, e0, e1, 0, E);
+    else
+      hipLaunchKernelGGL(kern, grid, block, 0, s, E);
+  };
+  band ? launch(k_probe_encode420<false, true>) : launch(k_probe_encode420<false>);
   return check_launch("k_probe_encode420");
 }
 
@@ -929,15 +1127,16 @@ extern "C" int hic_probe_encode420_slots(const uint8_t *rgb, int64_t H, int64_t 
   E.nstrips = (int)(W / 512);
   E.wlast = 512;
   E.nunits = E.nstrips * (int)(H / 16);
-  const int order = knob(HIC_KNOB_ENCODE_ORDER);
-  E.xcd = (order >> 1) & 1;
-  E.alt = (order >> 2) & 1;
-  const dim3 grid((unsigned)((E.nunits + HIC_ENC_WPB - 1) / HIC_ENC_WPB)), block(64 * HIC_ENC_WPB);
+  const bool band = enc_order(E);
+  const dim3 grid = enc_grid(E, band), block(64 * HIC_ENC_WPB);
   const hipStream_t s = as_stream(stream);
   const hipEvent_t e0 = static_cast<hipEvent_t>(ev_start), e1 = static_cast<hipEvent_t>(ev_stop);
-  if (e0 || e1)
-    hipExtLaunchKernelGGL(k_probe_encode420<true>, grid, block, 0, s, e0, e1, 0, E);
-  else
-    hipLaunchKernelGGL(k_probe_encode420<true>, grid, block, 0, s, E);
+  auto launch = [&](auto kern) {
+    if (e0 || e1)
+      hipExtLaunchKernelGGL(kern, grid, block, 0, s, e0, e1, 0, E);
+    else
+      hipLaunchKernelGGL(kern, grid, block, 0, s, E);
+  };
+  band ? launch(k_probe_encode420<true, true>) : launch(k_probe_encode420<true>);
   return check_launch("k_probe_encode420<slots>");
 }

@@ -80,7 +80,8 @@ int hic_device_count(int *h_n);
  * (-1, the default, is a no-op: resetting every knob 0 .. HIC_KNOB_COUNT - 1 works) */
 #define HIC_KNOB_ENCODE_ORDER 13     /* hic_encode420_u8 unit order: 0 row-major; + 2: workgroups remapped XCD-major (neighbouring units on one XCD's L2); + 4: odd unit rows run their colour rows bottom-up (the halo rows two unit rows share fetched at the same time); default 6; odd values refused */
 /* 14, 15: retired in round 5 with the packed-float32 transforms (refused, -1 a no-op) */
-#define HIC_KNOB_COUNT 16
+#define HIC_KNOB_ENCODE_BAND 16      /* hic_encode420_u8 / _seg / _slots: 1 (default): a workgroup is four vertically stacked units of one strip, workgroups band-major (XCD-major with encode_order bit 1), and the pyrDown halo rows two of its units share are converted once and exchanged through LDS (encode_order bit 2 has no effect then); 0: one unit per wave in the encode_order order, every wave its own 19 rows (the kernel before round 8; hic_encode420_batch_u8 always) */
+#define HIC_KNOB_COUNT 17
 int hic_set_knob(int knob, int value);
 int hic_get_knob(int knob, int *h_value);
 /* Synchronises `stream`; returns HIC_ERR_HIP if an earlier async launch failed. */
@@ -99,7 +100,8 @@ int hic_stream_sync(void *stream);
  *  waves_per_cu: persistent grid size (0 = default: 16 for the copy, 12 for the plane).
  *  hic_probe_encode420: hic_encode420_u8's byte pattern without its arithmetic, on a
  *    whole H x W RGB image (W % 512 == 0, H % 16 == 0): the same grid, unit order
- *    (knob encode_order) and 19 row loads per 16-row unit, the LDS stage and 1 KiB
+ *    (knob encode_order) and row loads per 16-row unit (19, or in stacked bands 16
+ *    plus the halo rows the unit has no neighbour for), the LDS stage and 1 KiB
  *    nontemporal stores of the Y / Cr / Cb blocks (coef_*: the encoder's outputs'
  *    sizes) and one 24 B record per tile (rec_y: H/8 * W/512 records, rec_c: H/16 *
  *    W/512): the fused kernel's memory floor. */
