@@ -166,15 +166,7 @@ __device__ __forceinline__ void ycc4(uint32_t w0, uint32_t w1, uint32_t w2, cons
   }
 }
 
-template <typename T>
-__device__ __forceinline__ void st_plane(T *p, T v, bool nt) {
-  if (nt)
-    __builtin_nontemporal_store(v, p);
-  else
-    *p = v;
-}
-
-template <int kSegC, bool NT = false>
+template <int kSegC>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kSegC == 8 ? 4 : 3))) void k_rgb_ycrcb420_walk(const uint8_t *__restrict__ rgb, int in_row0, int in_rows,
                                                            int H, int W, int out_row0, int out_rows,
                                                            uint8_t *__restrict__ Y, uint8_t *__restrict__ Cr,
@@ -258,9 +250,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kSegC == 8 
       const int gy = gy0 + r;
       if (EDGE) {
         if (owner && gy >= yw0 && gy < yw1)
-          st_plane(reinterpret_cast<uint32_t *>(Y + (int64_t)(gy - out_row0) * W + 4 * q), yq, NT);
+          *reinterpret_cast<uint32_t *>(Y + (int64_t)(gy - out_row0) * W + 4 * q) = yq;
       } else if (r >= 2 && r < 2 + 2 * kSegC) {
-        st_plane(reinterpret_cast<uint32_t *>(Y + (int64_t)(gy - out_row0) * W + 4 * q), yq, NT);
+        *reinterpret_cast<uint32_t *>(Y + (int64_t)(gy - out_row0) * W + 4 * q) = yq;
       }
       // neighbours: pixels x-2, x-1 from the left quad, x+4 from the right quad
       uint32_t l2 = shr1(c[2]), l1 = shr1(c[3]), rt = shl1(c[0]);
@@ -282,8 +274,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kSegC == 8 
         const uint32_t v2 = pk_add_u16(pk_taps5(h2[a], h2[a + 1], h2[a + 2], h2[a + 3], h2[a + 4], k4, k6), k128);
         const int64_t o = (int64_t)(oyl0 + k) * dw + 2 * q;
         // (v + 128) >> 8 = the high byte of each half (<= 255: no saturation)
-        st_plane(reinterpret_cast<uint16_t *>(Cr + o), (uint16_t)__builtin_amdgcn_perm(v2, v0, 0x0C0C0501u), NT);
-        st_plane(reinterpret_cast<uint16_t *>(Cb + o), (uint16_t)__builtin_amdgcn_perm(v2, v0, 0x0C0C0703u), NT);
+        // (addresses before values: the evaluation order the kernel was tuned with)
+        uint16_t *pr = reinterpret_cast<uint16_t *>(Cr + o), *pb = reinterpret_cast<uint16_t *>(Cb + o);
+        *pr = (uint16_t)__builtin_amdgcn_perm(v2, v0, 0x0C0C0501u);
+        *pb = (uint16_t)__builtin_amdgcn_perm(v2, v0, 0x0C0C0703u);
       }
     }
   };
@@ -549,10 +543,6 @@ extern "C" int hic_rgb_to_ycrcb420_rows(const uint8_t *rgb_rows, int64_t in_row0
       hipLaunchKernelGGL(k_rgb_ycrcb420_walk<16>, grid, dim3(256), 0, as_stream(stream), rgb_rows, (int)in_row0,
                          (int)in_rows, (int)H, (int)W, (int)out_row0, (int)out_rows, y, cr, cb, (int)(c1 - c0),
                          nstrips, nwaves);
-    else if (knob(HIC_KNOB_COLOR_NT) == 1)  // A/B: nontemporal plane stores
-      hipLaunchKernelGGL((k_rgb_ycrcb420_walk<8, true>), grid, dim3(256), 0, as_stream(stream), rgb_rows,
-                         (int)in_row0, (int)in_rows, (int)H, (int)W, (int)out_row0, (int)out_rows, y, cr, cb,
-                         (int)(c1 - c0), nstrips, nwaves);
     else
       hipLaunchKernelGGL(k_rgb_ycrcb420_walk<8>, grid, dim3(256), 0, as_stream(stream), rgb_rows, (int)in_row0,
                          (int)in_rows, (int)H, (int)W, (int)out_row0, (int)out_rows, y, cr, cb, (int)(c1 - c0),

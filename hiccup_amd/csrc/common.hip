@@ -17,7 +17,6 @@ int knob(int k) {
   switch (k) {
     case HIC_KNOB_DCT_PATH: return 1;
     case HIC_KNOB_COLOR_SEG: return 8;
-    case HIC_KNOB_RLE_NT: return 1;
     case HIC_KNOB_ENCODE_ORDER: return 6;  // XCD-major workgroups, odd unit rows bottom-up
     case HIC_KNOB_ENCODE_BAND: return 1;   // workgroups of four stacked units (halo rows through LDS)
     default: return k == HIC_KNOB_DCT_WAVES_PER_CU ? -1 : 0;
@@ -89,10 +88,12 @@ extern "C" int hic_set_knob(int k, int value) {
   if (k == HIC_KNOB_DCT_PATH && value != -1 && !(value >= 0 && value <= 2))
     return hic::arg_error("dct path %d (0 exact, 1 / 2 float64 AAN)", value);
   if (k == HIC_KNOB_COLOR_SEG && value != -1 && value != 8 && value != 16) return hic::arg_error("colour segment");
-  // retired knobs (measured slower, removed in rounds 4-5: 9-12 encode waves / nontemporal
-  // stores / integer-MFMA transforms, 14-15 the packed-float32 transforms): -1 (the
-  // default) is accepted as a no-op, so a caller resetting every knob still can
-  if ((k >= 9 && k <= 12) || k == 14 || k == 15) {
+  // retired knobs (4-6 nontemporal against plain stores in the colour kernel, the RLE
+  // emit and the RLE decode: only the defaults remain; measured slower, removed in
+  // rounds 4-5: 9-12 encode waves / nontemporal stores / integer-MFMA transforms, 14-15
+  // the packed-float32 transforms): -1 (the default) is accepted as a no-op, so a caller
+  // resetting every knob still can
+  if ((k >= 4 && k <= 6) || (k >= 9 && k <= 12) || k == 14 || k == 15) {
     if (value == -1) return HIC_OK;
     return hic::arg_error("knob %d is retired", k);
   }

@@ -1013,32 +1013,89 @@ extern "C" int hic_dequant_idct_u8(const void *coef, int layout, int64_t H, int6
   return arg_error("layout");
 }
 
+// ---- the fused tile decoders: six entry points, one launch of k_rld_idct_indexed.
+// What a launch decodes, and from which kind of stream:
+struct DecLaunch {
+  DecPlane p[2];         // the plane, or the two planes of a chroma pair (one table, one shape)
+  int nplanes;
+  int64_t H, W;
+  int table_id;
+  int64_t out_stride;    // of every plane's `out` (the RGB form: of the interleaved pixels)
+  bool rgb;              // luma straight to RGB: p[0].out is the pixels, cr / cb the decoded,
+  const uint8_t *cr;     // upsampled chroma planes it reads
+  const uint8_t *cb;
+  bool slots;            // the symbols are in the slot layout (slots.h) and `index` is the close's
+  int records_per_tile;  // int32 record index, 1 or 2 records per tile; otherwise a tile index
+};
+
+// Every check before any device call; then the grid and the kernel for (table, whole
+// blocks, RGB, stream kind).
+static int launch_rld_idct(const DecLaunch &d, void *stream) {
+  for (int k = 0; k < d.nplanes; ++k) {
+    const DecPlane &p = d.p[k];
+    char who[16] = "";
+    if (d.nplanes > 1) snprintf(who, sizeof who, "plane %d: ", k);
+    if (!p.sym_len || !p.sym_val || !p.d_nsym || !p.dc_diff || !p.index || !p.out || !p.d_status ||
+        (d.rgb && (!d.cr || !d.cb)))
+      return arg_error("%snull pointer", who);
+    // the gathers read the symbols as uint4s
+    if (!aligned(p.sym_len, 16) || !aligned(p.sym_val, 16))
+      return arg_error("%s%s arrays must be 16-byte aligned", who, d.slots ? "slot" : "symbol");
+  }
+  if (d.rgb) {
+    // the RGB form has no ragged path: whole 8x8 blocks, 8-byte pixel stores
+    if (!dims_ok(d.H, d.W) || d.H % 8 || d.W % 8) return arg_error("plane shape (H, W multiples of 8)");
+    if (d.out_stride < 3 * d.W || d.out_stride % 8 || !aligned(d.p[0].out, 8))
+      return arg_error("rgb stride / alignment (8 B)");
+    if (!aligned(d.cr, 4) || !aligned(d.cb, 4)) return arg_error("chroma planes must be 4-byte aligned");
+  } else if (!dims_ok(d.H, d.W) || d.out_stride < d.W) {
+    return arg_error("plane shape / stride");
+  }
+  if (d.table_id != HIC_TABLE_LUMINANCE && d.table_id != HIC_TABLE_CHROMINANCE) return arg_error("table_id");
+  const int nbx = (int)((d.W + 7) / 8);
+  const int64_t nblk = (int64_t)nbx * ((d.H + 7) / 8);
+  if (nblk * 63 >= ((int64_t)1 << 31)) return arg_error("plane too large (AC stream >= 2^31)");
+  if (d.slots) {
+    if (d.records_per_tile != 1 && d.records_per_tile != 2) return arg_error("records_per_tile must be 1 or 2");
+    if (nblk % (64 / d.records_per_tile)) return arg_error("the plane's blocks must form whole records");
+  }
+  bool fast = d.H % 8 == 0 && d.W % 8 == 0 && d.out_stride % 8 == 0;
+  for (int k = 0; k < d.nplanes; ++k) fast = fast && aligned(d.p[k].out, 8);
+  const int64_t ntiles = (nblk + 63) / 64;
+  const dim3 grid((unsigned)((d.nplanes * ntiles + 3) / 4)), block(256);
+  hipStream_t s = as_stream(stream);
+  const DecPlane &a = d.p[0], second = d.nplanes > 1 ? d.p[1] : DecPlane{};
+  const int rsh = d.slots && d.records_per_tile == 2 ? 1 : 0;
+#define HIC_DEC(T, F, R, S)                                                                                         \
+  hipLaunchKernelGGL((k_rld_idct_indexed<T, F, R, S>), grid, block, 0, s, a.sym_len, a.sym_val, a.d_nsym, a.dc_diff, \
+                     a.index, (int)d.H, (int)d.W, nbx, nblk, a.out, d.out_stride, a.d_status, d.cr, d.cb, second, rsh)
+#define HIC_DEC_PLANES(S)                                      \
+  do {                                                         \
+    if (d.table_id == 0 && fast) HIC_DEC(0, true, false, S);   \
+    else if (d.table_id == 0) HIC_DEC(0, false, false, S);     \
+    else if (fast) HIC_DEC(1, true, false, S);                 \
+    else HIC_DEC(1, false, false, S);                          \
+  } while (0)
+  if (d.rgb && d.slots) HIC_DEC(0, true, true, true);  // (the checks above leave the RGB form whole blocks)
+  else if (d.rgb) HIC_DEC(0, true, true, false);
+  else if (d.slots) HIC_DEC_PLANES(true);
+  else HIC_DEC_PLANES(false);
+#undef HIC_DEC_PLANES
+#undef HIC_DEC
+  return check_launch("k_rld_idct_indexed");
+}
+
+// the slot layout's record index is int32; the kernel takes either index through one pointer
+static const int64_t *slot_ix(const int32_t *d_index) { return reinterpret_cast<const int64_t *>(d_index); }
+
 extern "C" int hic_rle_decode_idct_u8_indexed(const uint8_t *sym_len, const int16_t *sym_val, const int64_t *d_nsym,
                                               const int32_t *dc_diff, const int64_t *d_index, int64_t H, int64_t W,
                                               int table_id, uint8_t *out, int64_t out_stride, int64_t *d_status,
                                               void *stream) {
-  if (!sym_len || !sym_val || !d_nsym || !dc_diff || !d_index || !out || !d_status) return arg_error("null pointer");
-  if (!dims_ok(H, W) || out_stride < W) return arg_error("plane shape / stride");
-  if (table_id != HIC_TABLE_LUMINANCE && table_id != HIC_TABLE_CHROMINANCE) return arg_error("table_id");
-  if ((reinterpret_cast<uintptr_t>(sym_len) | reinterpret_cast<uintptr_t>(sym_val)) % 16)
-    return arg_error("symbol arrays must be 16-byte aligned");
-  const int nbx = (int)((W + 7) / 8);
-  const int64_t nblk = (int64_t)nbx * ((H + 7) / 8);
-  if (nblk * 63 >= ((int64_t)1 << 31)) return arg_error("plane too large (AC stream >= 2^31)");
-  const bool fast = H % 8 == 0 && W % 8 == 0 && out_stride % 8 == 0 && aligned(out, 8);
-  const int64_t ntiles = (nblk + 63) / 64;
-  const dim3 grid((unsigned)((ntiles + 3) / 4)), block(256);
-  hipStream_t s = as_stream(stream);
-  const int h = (int)H, w = (int)W;
-#define HIC_RI(T, F)                                                                                              \
-  hipLaunchKernelGGL((k_rld_idct_indexed<T, F>), grid, block, 0, s, sym_len, sym_val, d_nsym, dc_diff, d_index, h, \
-                     w, nbx, nblk, out, out_stride, d_status)
-  if (table_id == 0 && fast) HIC_RI(0, true);
-  else if (table_id == 0) HIC_RI(0, false);
-  else if (fast) HIC_RI(1, true);
-  else HIC_RI(1, false);
-#undef HIC_RI
-  return check_launch("k_rld_idct_indexed");
+  DecLaunch d{};
+  d.p[0] = DecPlane{sym_len, sym_val, d_nsym, dc_diff, d_index, out, d_status};
+  d.nplanes = 1, d.H = H, d.W = W, d.table_id = table_id, d.out_stride = out_stride;
+  return launch_rld_idct(d, stream);
 }
 
 extern "C" int hic_rle_decode_idct_u8_indexed_pair(const uint8_t *const *h_sym_len, const int16_t *const *h_sym_val,
@@ -1048,92 +1105,33 @@ extern "C" int hic_rle_decode_idct_u8_indexed_pair(const uint8_t *const *h_sym_l
                                                    void *stream) {
   if (!h_sym_len || !h_sym_val || !h_d_nsym || !h_dc_diff || !h_d_index || !h_out || !h_d_status)
     return arg_error("null pointer");
-  for (int k = 0; k < 2; ++k) {
-    if (!h_sym_len[k] || !h_sym_val[k] || !h_d_nsym[k] || !h_dc_diff[k] || !h_d_index[k] || !h_out[k] ||
-        !h_d_status[k])
-      return arg_error("plane %d: null pointer", k);
-    if ((reinterpret_cast<uintptr_t>(h_sym_len[k]) | reinterpret_cast<uintptr_t>(h_sym_val[k])) % 16)
-      return arg_error("plane %d: symbol arrays must be 16-byte aligned", k);
-  }
-  if (!dims_ok(H, W) || out_stride < W) return arg_error("plane shape / stride");
-  if (table_id != HIC_TABLE_LUMINANCE && table_id != HIC_TABLE_CHROMINANCE) return arg_error("table_id");
-  const int nbx = (int)((W + 7) / 8);
-  const int64_t nblk = (int64_t)nbx * ((H + 7) / 8);
-  if (nblk * 63 >= ((int64_t)1 << 31)) return arg_error("plane too large (AC stream >= 2^31)");
-  const bool fast = H % 8 == 0 && W % 8 == 0 && out_stride % 8 == 0 && aligned(h_out[0], 8) && aligned(h_out[1], 8);
-  const int64_t ntiles = (nblk + 63) / 64;
-  const dim3 grid((unsigned)((2 * ntiles + 3) / 4)), block(256);
-  hipStream_t s = as_stream(stream);
-  const DecPlane p1{h_sym_len[1], h_sym_val[1], h_d_nsym[1], h_dc_diff[1], h_d_index[1], h_out[1], h_d_status[1]};
-#define HIC_RI2(T, F)                                                                                              \
-  hipLaunchKernelGGL((k_rld_idct_indexed<T, F>), grid, block, 0, s, h_sym_len[0], h_sym_val[0], h_d_nsym[0],     \
-                     h_dc_diff[0], h_d_index[0], (int)H, (int)W, nbx, nblk, h_out[0], out_stride, h_d_status[0], \
-                     nullptr, nullptr, p1)
-  if (table_id == 0 && fast) HIC_RI2(0, true);
-  else if (table_id == 0) HIC_RI2(0, false);
-  else if (fast) HIC_RI2(1, true);
-  else HIC_RI2(1, false);
-#undef HIC_RI2
-  return check_launch("k_rld_idct_indexed<pair>");
+  DecLaunch d{};
+  for (int k = 0; k < 2; ++k)
+    d.p[k] = DecPlane{h_sym_len[k], h_sym_val[k], h_d_nsym[k], h_dc_diff[k], h_d_index[k], h_out[k], h_d_status[k]};
+  d.nplanes = 2, d.H = H, d.W = W, d.table_id = table_id, d.out_stride = out_stride;
+  return launch_rld_idct(d, stream);
 }
 
 extern "C" int hic_rle_decode_idct_rgb_indexed(const uint8_t *sym_len, const int16_t *sym_val, const int64_t *d_nsym,
                                                const int32_t *dc_diff, const int64_t *d_index, int64_t H, int64_t W,
                                                const uint8_t *cr, const uint8_t *cb, uint8_t *rgb, int64_t rgb_stride,
                                                int64_t *d_status, void *stream) {
-  if (!sym_len || !sym_val || !d_nsym || !dc_diff || !d_index || !cr || !cb || !rgb || !d_status)
-    return arg_error("null pointer");
-  if (!dims_ok(H, W) || H % 8 || W % 8) return arg_error("plane shape (H, W multiples of 8)");
-  if (rgb_stride < 3 * W || rgb_stride % 8 || !aligned(rgb, 8)) return arg_error("rgb stride / alignment (8 B)");
-  if (!aligned(cr, 4) || !aligned(cb, 4)) return arg_error("chroma planes must be 4-byte aligned");
-  if ((reinterpret_cast<uintptr_t>(sym_len) | reinterpret_cast<uintptr_t>(sym_val)) % 16)
-    return arg_error("symbol arrays must be 16-byte aligned");
-  const int nbx = (int)(W / 8);
-  const int64_t nblk = (int64_t)nbx * (H / 8);
-  if (nblk * 63 >= ((int64_t)1 << 31)) return arg_error("plane too large (AC stream >= 2^31)");
-  const int64_t ntiles = (nblk + 63) / 64;
-  hipLaunchKernelGGL((k_rld_idct_indexed<0, true, true>), dim3((unsigned)((ntiles + 3) / 4)), dim3(256), 0,
-                     as_stream(stream), sym_len, sym_val, d_nsym, dc_diff, d_index, (int)H, (int)W, nbx, nblk, rgb,
-                     rgb_stride, d_status, cr, cb);
-  return check_launch("k_rld_idct_indexed<rgb>");
-}
-
-// ---- the slot-layout decoders (slots.h): the *_indexed entry points above, reading
-// the slots through the close's record index
-static int slots_args(const void *slot_len, const void *slot_val, int records_per_tile, int64_t nblk) {
-  if (records_per_tile != 1 && records_per_tile != 2) return arg_error("records_per_tile must be 1 or 2");
-  if (nblk % (64 / records_per_tile)) return arg_error("the plane's blocks must form whole records");
-  if ((reinterpret_cast<uintptr_t>(slot_len) | reinterpret_cast<uintptr_t>(slot_val)) % 16)
-    return arg_error("slot arrays must be 16-byte aligned");
-  return HIC_OK;
+  DecLaunch d{};
+  d.p[0] = DecPlane{sym_len, sym_val, d_nsym, dc_diff, d_index, rgb, d_status};
+  d.nplanes = 1, d.H = H, d.W = W, d.table_id = HIC_TABLE_LUMINANCE, d.out_stride = rgb_stride;
+  d.rgb = true, d.cr = cr, d.cb = cb;
+  return launch_rld_idct(d, stream);
 }
 
 extern "C" int hic_rle_decode_idct_u8_slots(const uint8_t *slot_len, const int16_t *slot_val, const int64_t *d_nsym,
                                             const int32_t *dc_diff, const int32_t *d_index, int records_per_tile,
                                             int64_t H, int64_t W, int table_id, uint8_t *out, int64_t out_stride,
                                             int64_t *d_status, void *stream) {
-  if (!slot_len || !slot_val || !d_nsym || !dc_diff || !d_index || !out || !d_status) return arg_error("null pointer");
-  if (!dims_ok(H, W) || out_stride < W) return arg_error("plane shape / stride");
-  if (table_id != HIC_TABLE_LUMINANCE && table_id != HIC_TABLE_CHROMINANCE) return arg_error("table_id");
-  const int nbx = (int)((W + 7) / 8);
-  const int64_t nblk = (int64_t)nbx * ((H + 7) / 8);
-  if (nblk * 63 >= ((int64_t)1 << 31)) return arg_error("plane too large (AC stream >= 2^31)");
-  if (int e = slots_args(slot_len, slot_val, records_per_tile, nblk)) return e;
-  const bool fast = H % 8 == 0 && W % 8 == 0 && out_stride % 8 == 0 && aligned(out, 8);
-  const int64_t ntiles = (nblk + 63) / 64;
-  const dim3 grid((unsigned)((ntiles + 3) / 4)), block(256);
-  hipStream_t s = as_stream(stream);
-  const int h = (int)H, w = (int)W, rsh = records_per_tile == 2 ? 1 : 0;
-  const int64_t *ix = reinterpret_cast<const int64_t *>(d_index);
-#define HIC_RS(T, F)                                                                                                \
-  hipLaunchKernelGGL((k_rld_idct_indexed<T, F, false, true>), grid, block, 0, s, slot_len, slot_val, d_nsym, dc_diff, \
-                     ix, h, w, nbx, nblk, out, out_stride, d_status, nullptr, nullptr, DecPlane{}, rsh)
-  if (table_id == 0 && fast) HIC_RS(0, true);
-  else if (table_id == 0) HIC_RS(0, false);
-  else if (fast) HIC_RS(1, true);
-  else HIC_RS(1, false);
-#undef HIC_RS
-  return check_launch("k_rld_idct_indexed<slots>");
+  DecLaunch d{};
+  d.p[0] = DecPlane{slot_len, slot_val, d_nsym, dc_diff, slot_ix(d_index), out, d_status};
+  d.nplanes = 1, d.H = H, d.W = W, d.table_id = table_id, d.out_stride = out_stride;
+  d.slots = true, d.records_per_tile = records_per_tile;
+  return launch_rld_idct(d, stream);
 }
 
 extern "C" int hic_rle_decode_idct_u8_slots_pair(const uint8_t *const *h_slot_len, const int16_t *const *h_slot_val,
@@ -1143,55 +1141,25 @@ extern "C" int hic_rle_decode_idct_u8_slots_pair(const uint8_t *const *h_slot_le
                                                  int64_t *const *h_d_status, void *stream) {
   if (!h_slot_len || !h_slot_val || !h_d_nsym || !h_dc_diff || !h_d_index || !h_out || !h_d_status)
     return arg_error("null pointer");
-  if (!dims_ok(H, W) || out_stride < W) return arg_error("plane shape / stride");
-  if (table_id != HIC_TABLE_LUMINANCE && table_id != HIC_TABLE_CHROMINANCE) return arg_error("table_id");
-  const int nbx = (int)((W + 7) / 8);
-  const int64_t nblk = (int64_t)nbx * ((H + 7) / 8);
-  if (nblk * 63 >= ((int64_t)1 << 31)) return arg_error("plane too large (AC stream >= 2^31)");
-  for (int k = 0; k < 2; ++k) {
-    if (!h_slot_len[k] || !h_slot_val[k] || !h_d_nsym[k] || !h_dc_diff[k] || !h_d_index[k] || !h_out[k] ||
-        !h_d_status[k])
-      return arg_error("plane %d: null pointer", k);
-    if (int e = slots_args(h_slot_len[k], h_slot_val[k], records_per_tile, nblk)) return e;
-  }
-  const bool fast = H % 8 == 0 && W % 8 == 0 && out_stride % 8 == 0 && aligned(h_out[0], 8) && aligned(h_out[1], 8);
-  const int64_t ntiles = (nblk + 63) / 64;
-  const dim3 grid((unsigned)((2 * ntiles + 3) / 4)), block(256);
-  hipStream_t s = as_stream(stream);
-  const int rsh = records_per_tile == 2 ? 1 : 0;
-  const DecPlane p1{h_slot_len[1], h_slot_val[1], h_d_nsym[1], h_dc_diff[1],
-                    reinterpret_cast<const int64_t *>(h_d_index[1]), h_out[1], h_d_status[1]};
-#define HIC_RS2(T, F)                                                                                              \
-  hipLaunchKernelGGL((k_rld_idct_indexed<T, F, false, true>), grid, block, 0, s, h_slot_len[0], h_slot_val[0],    \
-                     h_d_nsym[0], h_dc_diff[0], reinterpret_cast<const int64_t *>(h_d_index[0]), (int)H, (int)W, nbx, \
-                     nblk, h_out[0], out_stride, h_d_status[0], nullptr, nullptr, p1, rsh)
-  if (table_id == 0 && fast) HIC_RS2(0, true);
-  else if (table_id == 0) HIC_RS2(0, false);
-  else if (fast) HIC_RS2(1, true);
-  else HIC_RS2(1, false);
-#undef HIC_RS2
-  return check_launch("k_rld_idct_indexed<slots pair>");
+  DecLaunch d{};
+  for (int k = 0; k < 2; ++k)
+    d.p[k] = DecPlane{h_slot_len[k], h_slot_val[k], h_d_nsym[k], h_dc_diff[k], slot_ix(h_d_index[k]), h_out[k],
+                      h_d_status[k]};
+  d.nplanes = 2, d.H = H, d.W = W, d.table_id = table_id, d.out_stride = out_stride;
+  d.slots = true, d.records_per_tile = records_per_tile;
+  return launch_rld_idct(d, stream);
 }
 
 extern "C" int hic_rle_decode_idct_rgb_slots(const uint8_t *slot_len, const int16_t *slot_val, const int64_t *d_nsym,
                                              const int32_t *dc_diff, const int32_t *d_index, int records_per_tile,
                                              int64_t H, int64_t W, const uint8_t *cr, const uint8_t *cb, uint8_t *rgb,
                                              int64_t rgb_stride, int64_t *d_status, void *stream) {
-  if (!slot_len || !slot_val || !d_nsym || !dc_diff || !d_index || !cr || !cb || !rgb || !d_status)
-    return arg_error("null pointer");
-  if (!dims_ok(H, W) || H % 8 || W % 8) return arg_error("plane shape (H, W multiples of 8)");
-  if (rgb_stride < 3 * W || rgb_stride % 8 || !aligned(rgb, 8)) return arg_error("rgb stride / alignment (8 B)");
-  if (!aligned(cr, 4) || !aligned(cb, 4)) return arg_error("chroma planes must be 4-byte aligned");
-  const int nbx = (int)(W / 8);
-  const int64_t nblk = (int64_t)nbx * (H / 8);
-  if (nblk * 63 >= ((int64_t)1 << 31)) return arg_error("plane too large (AC stream >= 2^31)");
-  if (int e = slots_args(slot_len, slot_val, records_per_tile, nblk)) return e;
-  const int64_t ntiles = (nblk + 63) / 64;
-  hipLaunchKernelGGL((k_rld_idct_indexed<0, true, true, true>), dim3((unsigned)((ntiles + 3) / 4)), dim3(256), 0,
-                     as_stream(stream), slot_len, slot_val, d_nsym, dc_diff, reinterpret_cast<const int64_t *>(d_index),
-                     (int)H, (int)W, nbx, nblk, rgb, rgb_stride, d_status, cr, cb, DecPlane{},
-                     records_per_tile == 2 ? 1 : 0);
-  return check_launch("k_rld_idct_indexed<rgb slots>");
+  DecLaunch d{};
+  d.p[0] = DecPlane{slot_len, slot_val, d_nsym, dc_diff, slot_ix(d_index), rgb, d_status};
+  d.nplanes = 1, d.H = H, d.W = W, d.table_id = HIC_TABLE_LUMINANCE, d.out_stride = rgb_stride;
+  d.rgb = true, d.cr = cr, d.cb = cb;
+  d.slots = true, d.records_per_tile = records_per_tile;
+  return launch_rld_idct(d, stream);
 }
 
 extern "C" int hic_dct2_f64(const double *in, int64_t nblk, double *out, void *stream) {

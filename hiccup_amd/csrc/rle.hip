@@ -413,7 +413,7 @@ __global__ __launch_bounds__(256) void k_rle_tile16(const int16_t *__restrict__ 
 // by the whole wave.
 constexpr int kWSyms = 4096;  // staged symbols per wave (a dense tile has <= 64 * 63)
 
-template <int MF, bool NT>
+template <int MF>
 // w: this lane's block in registers; blk: the same block in global memory, read
 // for lane-varying coefficient indices (keeps w out of scratch).
 __device__ __forceinline__ void emit_tile16(const uint32_t (&w)[32], const int16_t *__restrict__ blk, bool valid,
@@ -541,8 +541,9 @@ __device__ __forceinline__ void emit_tile16(const uint32_t (&w)[32], const int16
   // (no vmcnt drain here: the copy-out reads only this wave's LDS stage, so the
   // next tile's prefetch stays in flight across it)
   if (staged) {
-    copy_out_wave16<uint8_t, NT>(s_len, lo, sym_len, o_tile, (int)total, cap);
-    copy_out_wave16<int16_t, NT>(s_val, vo, sym_val, o_tile, (int)total, cap);
+    // nontemporal: the symbols are streaming output, not read again in this launch
+    copy_out_wave16<uint8_t, true>(s_len, lo, sym_len, o_tile, (int)total, cap);
+    copy_out_wave16<int16_t, true>(s_val, vo, sym_val, o_tile, (int)total, cap);
   } else {
     // long carried runs: the whole wave writes each lane's fillers
     uint64_t m = __ballot(nf0 > 0);
@@ -762,7 +763,7 @@ __global__ __launch_bounds__(kScan16T) void k_rle_scan16b(RleJobs16 jobs, uint32
   if (s_fail && threadIdx.x == 0) put_granule(gran + 3 * np, 1, tag);
 }
 
-template <int MF, bool NT>
+template <int MF>
 __global__ __launch_bounds__(256) void k_rle_emit16b(RleJobs16 jobs) {
   // per wave: kWSyms symbols + 16-byte alignment slack + the dummy slot
   __shared__ __attribute__((aligned(16))) uint8_t s_len_all[4][kWSyms + 32];
@@ -877,7 +878,7 @@ __global__ __launch_bounds__(256) void k_rle_emit16b(RleJobs16 jobs) {
       else
         J.dc_diff[b] = (J.stitch && J.stitch[2]) ? dc - (int)J.stitch[3] : dc;
     }
-    emit_tile16<MF, NT>(cur.w, J.blocks + (valid ? b : 0) * 64, valid, b, J.nblk, M, cur.off, cur.prev,
+    emit_tile16<MF>(cur.w, J.blocks + (valid ? b : 0) * 64, valid, b, J.nblk, M, cur.off, cur.prev,
                     s_len_all[wv], s_val_all[wv], J.sym_len, J.sym_val, J.cap);
     if (gn >= jobs.total_tiles) break;
     g = gn;
@@ -1214,7 +1215,6 @@ __device__ __forceinline__ void put_block_part(int16_t *__restrict__ blocks, int
   }
 }
 
-template <bool NT>
 __global__ __launch_bounds__(kTB) void k_rld_blocks16(const uint8_t *__restrict__ sym_len,
                                                       const int16_t *__restrict__ sym_val, int64_t nsym,
                                                       const int64_t *__restrict__ tile_off, int n_ac,
@@ -1290,14 +1290,7 @@ __global__ __launch_bounds__(kTB) void k_rld_blocks16(const uint8_t *__restrict_
       const int64_t b = wb0 + bi;
       const int f = (int)(b * 63);
       if (f >= P0 && f + 62 < P1) {
-        if (NT) {  // nontemporal: a 16K plane's blocks overflow every cache level
-          typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-          const uint4 t = s_win[i];
-          const u32x4 v = {t.x, t.y, t.z, t.w};
-          __builtin_nontemporal_store(v, reinterpret_cast<u32x4 *>(blocks + b * 64) + c);
-        } else {
-          reinterpret_cast<uint4 *>(blocks + b * 64)[c] = s_win[i];
-        }
+        reinterpret_cast<uint4 *>(blocks + b * 64)[c] = s_win[i];
       } else {
         put_block_part(blocks, b, P0, P1, win + bi * 64, win[bi * 64], 8 * c, 8);
       }
@@ -1412,6 +1405,21 @@ int rle_encode(const T *blocks, int64_t nblk, StreamGeo g, int M, const int64_t 
 
 inline int64_t ntiles16(int64_t nblk) { return (nblk + kWT - 1) / kWT; }
 
+// uint8 lengths: fillers are max_len-1 <= 255 and residual runs < max_len
+int check_max_len(int max_len) {
+  if (max_len < 1 || max_len > 256) return arg_error("max_len must be in [1, 256] for uint8 symbol lengths");
+  return HIC_OK;
+}
+
+// What is wrong with the 16-bit blocks of one call or job (null: nothing).  any_null:
+// one of its required pointers is missing; the tile kernels read a block as uint4s.
+const char *blocks16_fault(bool any_null, const int16_t *blocks, int64_t nblk) {
+  if (any_null) return "null pointer";
+  if (nblk <= 0) return "nblk";
+  if (reinterpret_cast<uintptr_t>(blocks) & 15) return "blocks must be 16-byte aligned";
+  return nullptr;
+}
+
 int launch_tile16(const int16_t *blocks, int64_t nblk, int M, int64_t *tiles, hipStream_t s) {
   const dim3 grid((unsigned)((ntiles16(nblk) + 3) / 4));
   if (M == 15)
@@ -1473,27 +1481,11 @@ int encode_batch16(RleJobs16 &jobs, hipStream_t s) {
   const int64_t cap = HIC_EMIT_WPC > 0 ? HIC_EMIT_WPC * (int64_t)cu_count() : INT64_MAX;
   const int64_t waves = t0 < cap ? t0 : cap;
   const dim3 grid((unsigned)((waves + 3) / 4));
-  // nontemporal symbol stores unless knob RLE_NT = 0 (A/B)
-  const bool nt = knob(HIC_KNOB_RLE_NT) != 0;
-  if (jobs.M == 15 && nt)
-    hipLaunchKernelGGL((k_rle_emit16b<15, true>), grid, dim3(256), 0, s, jobs);
-  else if (jobs.M == 15)
-    hipLaunchKernelGGL((k_rle_emit16b<15, false>), grid, dim3(256), 0, s, jobs);
-  else if (nt)
-    hipLaunchKernelGGL((k_rle_emit16b<0, true>), grid, dim3(256), 0, s, jobs);
+  if (jobs.M == 15)
+    hipLaunchKernelGGL(k_rle_emit16b<15>, grid, dim3(256), 0, s, jobs);
   else
-    hipLaunchKernelGGL((k_rle_emit16b<0, false>), grid, dim3(256), 0, s, jobs);
+    hipLaunchKernelGGL(k_rle_emit16b<0>, grid, dim3(256), 0, s, jobs);
   return check_launch("k_rle_emit16b");
-}
-
-int encode_from_tiles16(const int16_t *blocks, int64_t nblk, int M, const int64_t *stitch, int32_t *dc_diff,
-                        uint8_t *sym_len, int16_t *sym_val, int64_t cap, int64_t *d_count, void *ws, hipStream_t s) {
-  RleJobs16 jobs{};
-  jobs.n = 1;
-  jobs.M = M;
-  jobs.j[0] = RleJob16{blocks, nblk, stitch, dc_diff, sym_len, sym_val, cap, d_count, static_cast<int64_t *>(ws), 0, 0,
-                       0, 0};
-  return encode_batch16(jobs, s);
 }
 
 inline StreamGeo block_geo(int64_t nblk, int L) { return StreamGeo{L, 1, L - 1, nblk * (L - 1)}; }
@@ -1562,12 +1554,7 @@ int rle_decode_blocks16(const uint8_t *sym_len, const int16_t *sym_val, int64_t 
   hipLaunchKernelGGL(k_dc_values16, dim3((unsigned)ntb), dim3(kTB), 0, s, dc_diff, nblk, dsum, stitch, dcval);
   if (int e = check_launch("k_dc_values16")) return e;
   if (nts > 0) {
-    const bool nt = knob(HIC_KNOB_RLD_NT) == 1;  // A/B: nontemporal block stores
-    if (nt)
-      hipLaunchKernelGGL(k_rld_blocks16<true>, dim3((unsigned)nts), dim3(kTB), 0, s, sym_len, sym_val, nsym, tsum,
-                       (int)(nblk * 63), stitch, dcval, blocks);
-    else
-      hipLaunchKernelGGL(k_rld_blocks16<false>, dim3((unsigned)nts), dim3(kTB), 0, s, sym_len, sym_val, nsym, tsum,
+    hipLaunchKernelGGL(k_rld_blocks16, dim3((unsigned)nts), dim3(kTB), 0, s, sym_len, sym_val, nsym, tsum,
                        (int)(nblk * 63), stitch, dcval, blocks);
     if (int e = check_launch("k_rld_blocks16")) return e;
   }
@@ -1600,7 +1587,7 @@ __global__ __launch_bounds__(256) void k_rle_index16(const int64_t *__restrict__
 
 // SLOTS: the symbols are in the slot layout (slots.h) and `index` is the close's
 // int32 record index (rsh: log2 records per 64-block tile).
-template <bool NT, bool SLOTS = false>
+template <bool SLOTS>
 __global__ __launch_bounds__(256) void k_rld_indexed16(const uint8_t *__restrict__ sym_len,
                                                        const int16_t *__restrict__ sym_val,
                                                        const int64_t *__restrict__ d_nsym,
@@ -1651,10 +1638,7 @@ __global__ __launch_bounds__(256) void k_rld_indexed16(const uint8_t *__restrict
     if (bb < nvb) {
       const uint4 x = tile[ci];
       u32x4 *o = reinterpret_cast<u32x4 *>(blocks + t * 64 * 64) + ci;
-      if (NT)
-        __builtin_nontemporal_store(u32x4{x.x, x.y, x.z, x.w}, o);
-      else
-        *o = u32x4{x.x, x.y, x.z, x.w};
+      *o = u32x4{x.x, x.y, x.z, x.w};
     }
   }
   if (t == ntiles - 1 && lane == 0) {
@@ -1705,19 +1689,46 @@ extern "C" int hic_rle_shard_summary_i32(const int32_t *blocks, int64_t nblk, in
   return rle_summary(blocks, nblk, block_len, workspace, d_summary, as_stream(stream));
 }
 
+// hic_rle_job16[n] -> the scan's and the emit's jobs, every job checked before anything
+// is launched.  h_row_blocks: each job's blocks per plane row (the row-segment form,
+// which writes no tile index), or null for whole tiles.
+static int rle_jobs16(int n, const hic_rle_job16 *jobs, const int64_t *h_row_blocks, int max_len, RleJobs16 &J) {
+  if (n < 1 || n > kMaxJobs || !jobs) return arg_error("1 <= n <= %d jobs", kMaxJobs);
+  if (int e = check_max_len(max_len)) return e;
+  J = RleJobs16{};
+  J.n = n;
+  J.M = max_len;
+  for (int k = 0; k < n; ++k) {
+    const hic_rle_job16 &a = jobs[k];
+    const bool null = !a.blocks || !a.dc_diff || !a.sym_len || !a.sym_val || !a.d_count || !a.workspace;
+    if (const char *f = blocks16_fault(null, a.blocks, a.nblk)) return arg_error("job %d: %s", k, f);
+    if (a.records_per_tile != 0 && a.records_per_tile != 1 && a.records_per_tile != 2)
+      return arg_error("job %d: records_per_tile must be 1 or 2", k);
+    const int64_t rb = h_row_blocks ? h_row_blocks[k] : 0;
+    if (h_row_blocks && (rb < 1 || a.nblk % rb)) return arg_error("job %d: row_blocks must divide nblk", k);
+    if (h_row_blocks && a.d_index) return arg_error("job %d: d_index is for hic_rle_encode_i16_tiles_batch", k);
+    if (a.d_index && a.d_stitch) return arg_error("job %d: d_index needs a job without d_stitch", k);
+    J.j[k] = RleJob16{a.blocks, a.nblk, a.d_stitch, a.dc_diff, a.sym_len, a.sym_val, a.sym_cap, a.d_count,
+                      static_cast<int64_t *>(a.workspace), 0, 0, 0, a.records_per_tile == 2 ? 1 : 0, rb, 0, 0,
+                      a.workspace_bytes, a.d_index};
+  }
+  return HIC_OK;
+}
+
 extern "C" int hic_rle_encode_i16(const int16_t *blocks, int64_t nblk, int block_len, int max_len,
                                   const int64_t *d_stitch, int32_t *dc_diff, uint8_t *sym_len, int16_t *sym_val,
                                   int64_t sym_cap, int64_t *d_count, void *workspace, void *stream) {
-  // uint8 lengths: fillers are max_len-1 <= 255 and residual runs < max_len
-  if (max_len < 1 || max_len > 256) return arg_error("max_len must be in [1, 256] for uint8 symbol lengths");
   if (block_len == 64 && (reinterpret_cast<uintptr_t>(blocks) & 15) == 0) {
-    if (!blocks || !dc_diff || !sym_len || !sym_val || !d_count || !workspace) return arg_error("null pointer");
-    if (nblk <= 0) return arg_error("nblk");
+    // the hot path: the tile pass, then the one-job batch
+    const hic_rle_job16 job{blocks, nblk, d_stitch, dc_diff, sym_len, sym_val,
+                            sym_cap, d_count, workspace, 0, 0, nullptr};
+    RleJobs16 J;
+    if (int e = rle_jobs16(1, &job, nullptr, max_len, J)) return e;
     hipStream_t s = as_stream(stream);
     if (int e = launch_tile16(blocks, nblk, max_len, static_cast<int64_t *>(workspace), s)) return e;
-    return encode_from_tiles16(blocks, nblk, max_len, d_stitch, dc_diff, sym_len, sym_val, sym_cap, d_count,
-                               workspace, s);
+    return encode_batch16(J, s);
   }
+  if (int e = check_max_len(max_len)) return e;
   if (block_len < 2) return arg_error("block_len");
   if (!dc_diff) return arg_error("null dc_diff");
   return rle_encode(blocks, nblk, block_geo(nblk, block_len), max_len, d_stitch, dc_diff, sym_len, sym_val, sym_cap,
@@ -1727,67 +1738,29 @@ extern "C" int hic_rle_encode_i16(const int16_t *blocks, int64_t nblk, int block
 extern "C" int hic_rle_encode_i16_tiles(const int16_t *blocks, int64_t nblk, int max_len, const int64_t *d_stitch,
                                         int32_t *dc_diff, uint8_t *sym_len, int16_t *sym_val, int64_t sym_cap,
                                         int64_t *d_count, void *workspace, void *stream) {
-  if (!blocks || !dc_diff || !sym_len || !sym_val || !d_count || !workspace) return arg_error("null pointer");
-  if (nblk <= 0) return arg_error("nblk");
-  if (max_len < 1 || max_len > 256) return arg_error("max_len must be in [1, 256] for uint8 symbol lengths");
-  if (reinterpret_cast<uintptr_t>(blocks) & 15) return arg_error("blocks must be 16-byte aligned");
-  return encode_from_tiles16(blocks, nblk, max_len, d_stitch, dc_diff, sym_len, sym_val, sym_cap, d_count, workspace,
-                             as_stream(stream));
+  const hic_rle_job16 job{blocks, nblk, d_stitch, dc_diff, sym_len, sym_val,
+                          sym_cap, d_count, workspace, 0, 0, nullptr};
+  return hic_rle_encode_i16_tiles_batch(1, &job, max_len, stream);
 }
 
 extern "C" int hic_rle_tile_records_i16(const int16_t *blocks, int64_t nblk, int max_len, void *workspace,
                                         void *stream) {
-  if (!blocks || !workspace) return arg_error("null pointer");
-  if (nblk <= 0) return arg_error("nblk");
-  if (max_len < 1 || max_len > 256) return arg_error("max_len must be in [1, 256] for uint8 symbol lengths");
-  if (reinterpret_cast<uintptr_t>(blocks) & 15) return arg_error("blocks must be 16-byte aligned");
+  if (const char *f = blocks16_fault(!blocks || !workspace, blocks, nblk)) return arg_error("%s", f);
+  if (int e = check_max_len(max_len)) return e;
   return launch_tile16(blocks, nblk, max_len, static_cast<int64_t *>(workspace), as_stream(stream));
 }
 
 extern "C" int hic_rle_encode_i16_tiles_batch(int n, const hic_rle_job16 *jobs, int max_len, void *stream) {
-  if (n < 1 || n > kMaxJobs || !jobs) return arg_error("1 <= n <= %d jobs", kMaxJobs);
-  if (max_len < 1 || max_len > 256) return arg_error("max_len must be in [1, 256] for uint8 symbol lengths");
-  RleJobs16 J{};
-  J.n = n;
-  J.M = max_len;
-  for (int k = 0; k < n; ++k) {
-    const hic_rle_job16 &a = jobs[k];
-    if (!a.blocks || !a.dc_diff || !a.sym_len || !a.sym_val || !a.d_count || !a.workspace)
-      return arg_error("job %d: null pointer", k);
-    if (a.nblk <= 0) return arg_error("job %d: nblk", k);
-    if (reinterpret_cast<uintptr_t>(a.blocks) & 15) return arg_error("job %d: blocks must be 16-byte aligned", k);
-    if (a.records_per_tile != 0 && a.records_per_tile != 1 && a.records_per_tile != 2)
-      return arg_error("job %d: records_per_tile must be 1 or 2", k);
-    if (a.d_index && a.d_stitch) return arg_error("job %d: d_index needs a job without d_stitch", k);
-    J.j[k] = RleJob16{a.blocks, a.nblk, a.d_stitch, a.dc_diff, a.sym_len, a.sym_val, a.sym_cap, a.d_count,
-                      static_cast<int64_t *>(a.workspace), 0, 0, 0, a.records_per_tile == 2 ? 1 : 0, 0, 0, 0,
-                      a.workspace_bytes, a.d_index};
-  }
+  RleJobs16 J;
+  if (int e = rle_jobs16(n, jobs, nullptr, max_len, J)) return e;
   return encode_batch16(J, as_stream(stream));
 }
 
 extern "C" int hic_rle_encode_i16_rows_batch(int n, const hic_rle_job16 *jobs, const int64_t *h_row_blocks,
                                              int max_len, void *stream) {
-  if (n < 1 || n > kMaxJobs || !jobs || !h_row_blocks) return arg_error("1 <= n <= %d jobs", kMaxJobs);
-  if (max_len < 1 || max_len > 256) return arg_error("max_len must be in [1, 256] for uint8 symbol lengths");
-  RleJobs16 J{};
-  J.n = n;
-  J.M = max_len;
-  for (int k = 0; k < n; ++k) {
-    const hic_rle_job16 &a = jobs[k];
-    if (!a.blocks || !a.dc_diff || !a.sym_len || !a.sym_val || !a.d_count || !a.workspace)
-      return arg_error("job %d: null pointer", k);
-    if (a.nblk <= 0) return arg_error("job %d: nblk", k);
-    if (reinterpret_cast<uintptr_t>(a.blocks) & 15) return arg_error("job %d: blocks must be 16-byte aligned", k);
-    if (a.records_per_tile != 0 && a.records_per_tile != 1 && a.records_per_tile != 2)
-      return arg_error("job %d: records_per_tile must be 1 or 2", k);
-    const int64_t rb = h_row_blocks[k];
-    if (rb < 1 || a.nblk % rb) return arg_error("job %d: row_blocks must divide nblk", k);
-    if (a.d_index) return arg_error("job %d: d_index is for hic_rle_encode_i16_tiles_batch", k);
-    J.j[k] = RleJob16{a.blocks, a.nblk, a.d_stitch, a.dc_diff, a.sym_len, a.sym_val, a.sym_cap, a.d_count,
-                      static_cast<int64_t *>(a.workspace), 0, 0, 0, a.records_per_tile == 2 ? 1 : 0, rb, 0, 0,
-                      a.workspace_bytes};
-  }
+  if (!h_row_blocks) return arg_error("null h_row_blocks");
+  RleJobs16 J;
+  if (int e = rle_jobs16(n, jobs, h_row_blocks, max_len, J)) return e;
   return encode_batch16(J, as_stream(stream));
 }
 
@@ -1803,23 +1776,35 @@ extern "C" int hic_rle_tile_index_i16(const int16_t *blocks, int64_t nblk, int r
   return check_launch("k_rle_index16");
 }
 
+// The one launch of k_rld_indexed16.  slots: the symbols are in the slot layout and
+// `index` is the close's int32 record index; otherwise a tile-index stream (`index`
+// int64 {offset, last nonzero, DC} per tile; records_per_tile unused).
+static int rld_indexed16(const uint8_t *sym_len, const int16_t *sym_val, const int64_t *d_nsym,
+                         const int32_t *dc_diff, int64_t nblk, bool slots, int records_per_tile, const void *index,
+                         int16_t *blocks, int64_t *d_status, void *stream) {
+  if (!sym_len || !sym_val || !d_nsym || !dc_diff || !index || !blocks || !d_status) return arg_error("null pointer");
+  if (nblk <= 0 || nblk * 63 >= ((int64_t)1 << 31)) return arg_error("nblk");
+  if (slots && records_per_tile != 1 && records_per_tile != 2) return arg_error("records_per_tile must be 1 or 2");
+  if (slots && nblk % (64 / records_per_tile)) return arg_error("nblk must hold whole records");
+  if ((reinterpret_cast<uintptr_t>(sym_len) | reinterpret_cast<uintptr_t>(sym_val) |
+       reinterpret_cast<uintptr_t>(blocks)) % 16)
+    return arg_error("%s arrays and blocks must be 16-byte aligned", slots ? "slot" : "symbol");
+  const int64_t ntiles = (nblk + 63) / 64;
+  const dim3 grid((unsigned)((ntiles + 3) / 4)), block(256);
+  const int64_t *ix = static_cast<const int64_t *>(index);
+  if (slots)
+    hipLaunchKernelGGL(k_rld_indexed16<true>, grid, block, 0, as_stream(stream), sym_len, sym_val, d_nsym, dc_diff,
+                       nblk, ix, blocks, d_status, records_per_tile == 2 ? 1 : 0);
+  else
+    hipLaunchKernelGGL(k_rld_indexed16<false>, grid, block, 0, as_stream(stream), sym_len, sym_val, d_nsym, dc_diff,
+                       nblk, ix, blocks, d_status, 0);
+  return check_launch(slots ? "k_rld_indexed16<slots>" : "k_rld_indexed16");
+}
+
 extern "C" int hic_rle_decode_i16_indexed(const uint8_t *sym_len, const int16_t *sym_val, const int64_t *d_nsym,
                                           const int32_t *dc_diff, int64_t nblk, const int64_t *d_index,
                                           int16_t *blocks, int64_t *d_status, void *stream) {
-  if (!sym_len || !sym_val || !d_nsym || !dc_diff || !d_index || !blocks || !d_status) return arg_error("null pointer");
-  if (nblk <= 0 || nblk * 63 >= ((int64_t)1 << 31)) return arg_error("nblk");
-  if ((reinterpret_cast<uintptr_t>(sym_len) | reinterpret_cast<uintptr_t>(sym_val) |
-       reinterpret_cast<uintptr_t>(blocks)) % 16)
-    return arg_error("symbol arrays and blocks must be 16-byte aligned");
-  const int64_t ntiles = (nblk + 63) / 64;
-  const dim3 grid((unsigned)((ntiles + 3) / 4)), block(256);
-  if (knob(HIC_KNOB_RLD_NT) == 1)
-    hipLaunchKernelGGL(k_rld_indexed16<true>, grid, block, 0, as_stream(stream), sym_len, sym_val, d_nsym, dc_diff, nblk,
-                       d_index, blocks, d_status);
-  else
-    hipLaunchKernelGGL(k_rld_indexed16<false>, grid, block, 0, as_stream(stream), sym_len, sym_val, d_nsym, dc_diff,
-                       nblk, d_index, blocks, d_status);
-  return check_launch("k_rld_indexed16");
+  return rld_indexed16(sym_len, sym_val, d_nsym, dc_diff, nblk, false, 0, d_index, blocks, d_status, stream);
 }
 
 // ---- slot layout (slots.h) ----
@@ -1833,7 +1818,7 @@ extern "C" size_t hic_rle_slots_workspace_bytes(int64_t nblk, int records_per_ti
 }
 
 // hic_slot_job[n] -> the scan / compaction jobs (validated, nothing launched on error)
-static int slot_jobs(int n, const hic_slot_job *jobs, int max_len, bool compact, RleJobs16 &J) {
+static int slot_jobs(int n, const hic_slot_job *jobs, int max_len, RleJobs16 &J) {
   if (n < 1 || n > kMaxJobs || !jobs) return arg_error("1 <= n <= %d jobs", kMaxJobs);
   if (max_len != 15) return arg_error("the slot layout needs max_len 15");
   J = RleJobs16{};
@@ -1874,13 +1859,12 @@ static int slot_jobs(int n, const hic_slot_job *jobs, int max_len, bool compact,
     r0 += J.j[k].nrec;
   }
   J.total_tiles = r0;
-  (void)compact;
   return HIC_OK;
 }
 
 extern "C" int hic_rle_slots_close(int n, const hic_slot_job *jobs, int max_len, void *stream) {
   RleJobs16 J;
-  if (int e = slot_jobs(n, jobs, max_len, false, J)) return e;
+  if (int e = slot_jobs(n, jobs, max_len, J)) return e;
   hipStream_t s = as_stream(stream);
   if (int e = scan_batch16<true>(J, s)) return e;
   hipLaunchKernelGGL(k_rle_scan_fold, dim3(1), dim3(64), 0, s, J);
@@ -1889,7 +1873,7 @@ extern "C" int hic_rle_slots_close(int n, const hic_slot_job *jobs, int max_len,
 
 extern "C" int hic_rle_slots_compact(int n, const hic_slot_job *jobs, int max_len, void *stream) {
   RleJobs16 J;
-  if (int e = slot_jobs(n, jobs, max_len, true, J)) return e;
+  if (int e = slot_jobs(n, jobs, max_len, J)) return e;
   const int64_t waves = J.total_tiles < 16 * (int64_t)cu_count() ? J.total_tiles : 16 * (int64_t)cu_count();
   hipLaunchKernelGGL(k_rle_slots_compact, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, as_stream(stream), J);
   return check_launch("k_rle_slots_compact");
@@ -1898,18 +1882,8 @@ extern "C" int hic_rle_slots_compact(int n, const hic_slot_job *jobs, int max_le
 extern "C" int hic_rle_decode_i16_slots(const uint8_t *slot_len, const int16_t *slot_val, const int64_t *d_nsym,
                                         const int32_t *dc_diff, int64_t nblk, int records_per_tile,
                                         const int32_t *d_index, int16_t *blocks, int64_t *d_status, void *stream) {
-  if (!slot_len || !slot_val || !d_nsym || !dc_diff || !d_index || !blocks || !d_status) return arg_error("null pointer");
-  if (nblk <= 0 || nblk * 63 >= ((int64_t)1 << 31)) return arg_error("nblk");
-  if (records_per_tile != 1 && records_per_tile != 2) return arg_error("records_per_tile must be 1 or 2");
-  if (nblk % (64 / records_per_tile)) return arg_error("nblk must hold whole records");
-  if ((reinterpret_cast<uintptr_t>(slot_len) | reinterpret_cast<uintptr_t>(slot_val) |
-       reinterpret_cast<uintptr_t>(blocks)) % 16)
-    return arg_error("slot arrays and blocks must be 16-byte aligned");
-  const int64_t ntiles = (nblk + 63) / 64;
-  hipLaunchKernelGGL((k_rld_indexed16<false, true>), dim3((unsigned)((ntiles + 3) / 4)), dim3(256), 0,
-                     as_stream(stream), slot_len, slot_val, d_nsym, dc_diff, nblk,
-                     reinterpret_cast<const int64_t *>(d_index), blocks, d_status, records_per_tile == 2 ? 1 : 0);
-  return check_launch("k_rld_indexed16<slots>");
+  return rld_indexed16(slot_len, slot_val, d_nsym, dc_diff, nblk, true, records_per_tile, d_index, blocks, d_status,
+                       stream);
 }
 
 extern "C" int hic_rle_shard_summary_records(const int16_t *blocks, int64_t nblk, int records_per_tile,

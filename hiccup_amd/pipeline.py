@@ -457,7 +457,8 @@ class Decoder:
 
     def decode(self, sym_len, sym_val, counts, dc, stream=None, index=None, keep_blocks=False, planes=False):
         """sym_len/sym_val/dc: {channel: device tensor}; counts: host ints per channel.
-        index: an Encoder(index=True)'s tile index ({channel: device tensor}); then
+        index: an Encoder(index=True)'s tile index ({channel: device tensor}), or a
+        slot-layout encoder's SlotIndex (the *_slots forms of the same kernels); then
         counts is the encoder's device count tensor (3,), nothing crosses to the
         host, and each plane is decoded and inverse-transformed by ONE kernel
         (hic_rle_decode_idct_u8_indexed: no tile pass, scans, DC chain or zig-zag
@@ -468,42 +469,57 @@ class Decoder:
         written); planes=True keeps the Y plane and the separate colour kernel."""
         s = device.stream_ptr(stream)
         lib = _lib.load()
-        if isinstance(index, SlotIndex):
-            return self._decode_slots(index, counts, dc, s, keep_blocks, planes)
+        # The stream kind.  A SlotIndex: the encoder's slots, read through the close's
+        # record index (the *_slots entry points, which also take the records per tile;
+        # the sym_len / sym_val arguments are not read).  A plain {channel: tensor}: the
+        # contiguous symbols and the tile index (*_indexed).
+        slots = isinstance(index, SlotIndex)
+        kind = "slots" if slots else "indexed"
+        if slots:
+            sym_len, sym_val = index.slot_len, index.slot_val
+
+        def src(i, k):
+            """Channel k's stream for an indexed entry point: (symbol lengths, values, device
+            count, DC differences), the index, and () or (records per tile,)."""
+            return ((sym_len[k].data_ptr(), sym_val[k].data_ptr(), counts.data_ptr() + 8 * i, dc[k].data_ptr()),
+                    index[k].data_ptr(), (index.rpt[k],) if slots else ())
+
+        def status(i):
+            return self.status.data_ptr() + 8 * i
+
+        def decode_plane(i, k):
+            """Channel k's symbols to its pixel plane, one kernel."""
+            sym, ix, rpt = src(i, k)
+            _lib.call("hic_rle_decode_idct_u8_" + kind, *sym, ix, *rpt, *self.shapes[k], TABLES[k],
+                      self.pix[k].data_ptr(), self.pix[k].stride(0), status(i), s)
+
+        cr, cb = self.pix["cr"].data_ptr(), self.pix["cb"].data_ptr()
         if index is not None and not keep_blocks and not planes and self.H % 8 == 0 and self.W % 8 == 0:
             # Cr and Cb in one launch (one tail), then Y straight to RGB
-            h, w = self.shapes["cr"]
             if self.chroma_pair:
-                pair = lambda f: (ctypes.c_void_p * 2)(*(f(i, k) for i, k in ((1, "cr"), (2, "cb"))))
-                _lib.call("hic_rle_decode_idct_u8_indexed_pair", pair(lambda i, k: sym_len[k].data_ptr()),
-                          pair(lambda i, k: sym_val[k].data_ptr()), pair(lambda i, k: counts.data_ptr() + 8 * i),
-                          pair(lambda i, k: dc[k].data_ptr()), pair(lambda i, k: index[k].data_ptr()), h, w,
-                          TABLES["cr"], pair(lambda i, k: self.pix[k].data_ptr()), self.pix["cr"].stride(0),
-                          pair(lambda i, k: self.status[i:i + 1].data_ptr()), s)
+                two = lambda a, b: (ctypes.c_void_p * 2)(a, b)  # noqa: E731
+                (sym_r, ix_r, rpt), (sym_b, ix_b, _) = src(1, "cr"), src(2, "cb")
+                _lib.call("hic_rle_decode_idct_u8_%s_pair" % kind, *map(two, sym_r, sym_b), two(ix_r, ix_b), *rpt,
+                          *self.shapes["cr"], TABLES["cr"], two(cr, cb), self.pix["cr"].stride(0),
+                          two(status(1), status(2)), s)
             else:
-                for i, k in ((1, "cr"), (2, "cb")):
-                    _lib.call("hic_rle_decode_idct_u8_indexed", device.ptr(sym_len[k]), device.ptr(sym_val[k]),
-                              ctypes.c_void_p(counts.data_ptr() + 8 * i), device.ptr(dc[k]), device.ptr(index[k]),
-                              h, w, TABLES[k], device.ptr(self.pix[k]), self.pix[k].stride(0),
-                              device.ptr(self.status[i:i + 1]), s)
-            _lib.call("hic_rle_decode_idct_rgb_indexed", device.ptr(sym_len["lum"]), device.ptr(sym_val["lum"]),
-                      ctypes.c_void_p(counts.data_ptr()), device.ptr(dc["lum"]), device.ptr(index["lum"]), self.H,
-                      self.W, device.ptr(self.pix["cr"]), device.ptr(self.pix["cb"]), device.ptr(self.rgb),
-                      self.rgb.stride(0), device.ptr(self.status[0:1]), s)
+                decode_plane(1, "cr")
+                decode_plane(2, "cb")
+            sym, ix, rpt = src(0, "lum")
+            _lib.call("hic_rle_decode_idct_rgb_" + kind, *sym, ix, *rpt, self.H, self.W, cr, cb, self.rgb.data_ptr(),
+                      self.rgb.stride(0), status(0), s)
             return self.rgb
         for i, k in enumerate(CHANNELS):
             h, w = self.shapes[k]
             n = self.blocks[k].shape[0]
             if index is not None and not keep_blocks:
-                _lib.call("hic_rle_decode_idct_u8_indexed", device.ptr(sym_len[k]), device.ptr(sym_val[k]),
-                          ctypes.c_void_p(counts.data_ptr() + 8 * i), device.ptr(dc[k]), device.ptr(index[k]), h, w,
-                          TABLES[k], device.ptr(self.pix[k]), self.pix[k].stride(0),
-                          device.ptr(self.status[i:i + 1]), s)
+                decode_plane(i, k)
                 continue
             if index is not None:
-                _lib.call("hic_rle_decode_i16_indexed", device.ptr(sym_len[k]), device.ptr(sym_val[k]),
-                          ctypes.c_void_p(counts.data_ptr() + 8 * i), device.ptr(dc[k]), n, device.ptr(index[k]),
-                          device.ptr(self.blocks[k]), device.ptr(self.status[i:i + 1]), s)
+                # (the block-level forms take the block count, then the records per tile,
+                # before the index)
+                sym, ix, rpt = src(i, k)
+                _lib.call("hic_rle_decode_i16_" + kind, *sym, n, *rpt, ix, self.blocks[k].data_ptr(), status(i), s)
             else:
                 nsym = int(counts[i])
                 need = lib.hic_rld_workspace_bytes(nsym, n)
@@ -515,48 +531,8 @@ class Decoder:
             _lib.call("hic_dequant_idct_u8", device.ptr(self.blocks[k]), _lib.LAYOUT_ZIGZAG_I16, h, w, TABLES[k],
                       device.ptr(self.pix[k]), self.pix[k].stride(0), s)
         h, w = self.shapes["cr"]
-        _lib.call("hic_ycrcb420_to_rgb", device.ptr(self.pix["lum"]), self.pix["lum"].stride(0),
-                  device.ptr(self.pix["cr"]), device.ptr(self.pix["cb"]), h, w, device.ptr(self.rgb), s)
-        return self.rgb
-
-    def _decode_slots(self, ix, counts, dc, s, keep_blocks, planes):
-        """decode() from a slot-layout encoder's stream (SlotIndex): the *_slots forms of
-        the indexed decoders."""
-        cnt = lambda i: ctypes.c_void_p(counts.data_ptr() + 8 * i)  # noqa: E731
-        if not keep_blocks and not planes and self.H % 8 == 0 and self.W % 8 == 0:
-            h, w = self.shapes["cr"]
-            if self.chroma_pair:
-                pair = lambda f: (ctypes.c_void_p * 2)(*(f(i, k) for i, k in ((1, "cr"), (2, "cb"))))  # noqa: E731
-                _lib.call("hic_rle_decode_idct_u8_slots_pair", pair(lambda i, k: ix.slot_len[k].data_ptr()),
-                          pair(lambda i, k: ix.slot_val[k].data_ptr()), pair(lambda i, k: counts.data_ptr() + 8 * i),
-                          pair(lambda i, k: dc[k].data_ptr()), pair(lambda i, k: ix.sidx[k].data_ptr()), ix.rpt["cr"],
-                          h, w, TABLES["cr"], pair(lambda i, k: self.pix[k].data_ptr()), self.pix["cr"].stride(0),
-                          pair(lambda i, k: self.status[i:i + 1].data_ptr()), s)
-            else:
-                for i, k in ((1, "cr"), (2, "cb")):
-                    _lib.call("hic_rle_decode_idct_u8_slots", device.ptr(ix.slot_len[k]), device.ptr(ix.slot_val[k]),
-                              cnt(i), device.ptr(dc[k]), device.ptr(ix.sidx[k]), ix.rpt[k], h, w, TABLES[k],
-                              device.ptr(self.pix[k]), self.pix[k].stride(0), device.ptr(self.status[i:i + 1]), s)
-            _lib.call("hic_rle_decode_idct_rgb_slots", device.ptr(ix.slot_len["lum"]), device.ptr(ix.slot_val["lum"]),
-                      cnt(0), device.ptr(dc["lum"]), device.ptr(ix.sidx["lum"]), ix.rpt["lum"], self.H, self.W,
-                      device.ptr(self.pix["cr"]), device.ptr(self.pix["cb"]), device.ptr(self.rgb),
-                      self.rgb.stride(0), device.ptr(self.status[0:1]), s)
-            return self.rgb
-        for i, k in enumerate(CHANNELS):
-            h, w = self.shapes[k]
-            if keep_blocks:
-                _lib.call("hic_rle_decode_i16_slots", device.ptr(ix.slot_len[k]), device.ptr(ix.slot_val[k]), cnt(i),
-                          device.ptr(dc[k]), self.blocks[k].shape[0], ix.rpt[k], device.ptr(ix.sidx[k]),
-                          device.ptr(self.blocks[k]), device.ptr(self.status[i:i + 1]), s)
-                _lib.call("hic_dequant_idct_u8", device.ptr(self.blocks[k]), _lib.LAYOUT_ZIGZAG_I16, h, w, TABLES[k],
-                          device.ptr(self.pix[k]), self.pix[k].stride(0), s)
-            else:
-                _lib.call("hic_rle_decode_idct_u8_slots", device.ptr(ix.slot_len[k]), device.ptr(ix.slot_val[k]),
-                          cnt(i), device.ptr(dc[k]), device.ptr(ix.sidx[k]), ix.rpt[k], h, w, TABLES[k],
-                          device.ptr(self.pix[k]), self.pix[k].stride(0), device.ptr(self.status[i:i + 1]), s)
-        h, w = self.shapes["cr"]
-        _lib.call("hic_ycrcb420_to_rgb", device.ptr(self.pix["lum"]), self.pix["lum"].stride(0),
-                  device.ptr(self.pix["cr"]), device.ptr(self.pix["cb"]), h, w, device.ptr(self.rgb), s)
+        _lib.call("hic_ycrcb420_to_rgb", device.ptr(self.pix["lum"]), self.pix["lum"].stride(0), cr, cb, h, w,
+                  device.ptr(self.rgb), s)
         return self.rgb
 
     def check_status(self):

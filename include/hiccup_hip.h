@@ -70,9 +70,8 @@ int hic_device_count(int *h_n);
 #define HIC_KNOB_DCT_WAVES_PER_CU 1 /* forward DCT persistent grid (waves per CU; 0 = one wave per set) */
 #define HIC_KNOB_COLOR_TILED 2      /* 1: LDS-tiled colour kernels instead of the wave-walk ones */
 #define HIC_KNOB_COLOR_SEG 3        /* wave-walk colour: chroma rows per segment (8 default, 16) */
-#define HIC_KNOB_COLOR_NT 4         /* 1: nontemporal plane stores in the colour kernel */
-#define HIC_KNOB_RLE_NT 5           /* 0: plain (not nontemporal) symbol stores in the RLE emit */
-#define HIC_KNOB_RLD_NT 6           /* 1: nontemporal block stores in the RLE decode */
+/* 4-6: retired (nontemporal against plain stores in the colour kernel, the RLE emit and
+ * the RLE decode: the measurements are done and the defaults are the code; refused, -1 a no-op) */
 #define HIC_KNOB_RLD_GENERIC 7      /* 1: the generic (any block size) RLE decode */
 #define HIC_KNOB_DEV 8              /* dev builds only (-DHIC_DEV): timing bits that skip work; refused otherwise */
 /* knobs 9-12 were retired in rounds 4-5 (encode waves / nontemporal stores / integer-MFMA

@@ -121,38 +121,144 @@ def test_round6_batch_entry_points_refuse_bad_jobs():
     assert lib.hic_zigzag8_blocks_i16(None, 8, 8, p, p, None) == _lib.HIC_ERR_ARG
 
 
+# Argument checks of the indexed / slot-layout decoders and the RLE batch encoders.
+# Every call below must be one the library refuses: an accepted call would launch a
+# kernel on these fake pointers on a machine with a GPU.
+P = 1 << 20  # never dereferenced (16-byte aligned); P + 8: misaligned for the symbol arrays
+KINDS = ("indexed", "slots")
+
+
+def _refused(fn, args, needle=None):
+    assert fn(*args) == _lib.HIC_ERR_ARG, (fn.__name__, args)
+    if needle is not None:
+        assert needle in _lib.last_error(), (fn.__name__, args, _lib.last_error())
+
+
+def _rpt(kind, rpt):
+    """The slot forms take records_per_tile after the index; the tile-index forms have none."""
+    return [rpt] if kind == "slots" else []
+
+
 def test_decode_rgb_indexed_arguments():
-    """hic_rle_decode_idct_rgb_indexed refuses what its kernel cannot take before
-    any device call: null pointers, planes that are not whole 8x8 blocks, a short or
-    unaligned RGB pitch, unaligned chroma planes."""
+    """hic_rle_decode_idct_rgb_indexed / _rgb_slots refuse what their kernel cannot take
+    before any device call: null pointers, planes that are not whole 8x8 blocks, a short
+    or unaligned RGB pitch, unaligned chroma planes, misaligned symbol arrays; the slot
+    form also a bad records_per_tile and blocks that do not form whole records."""
     lib = _lib.load()
-    p16 = ctypes.c_void_p(1 << 20)  # never dereferenced
-    args = lambda H, W, cr=p16, stride=None: (p16, p16, p16, p16, p16, H, W, cr, p16, p16,
-                                              3 * W if stride is None else stride, p16, None)
-    assert lib.hic_rle_decode_idct_rgb_indexed(None, *args(64, 64)[1:]) == _lib.HIC_ERR_ARG
-    assert "null pointer" in _lib.last_error()
-    for H, W in ((60, 64), (64, 62), (0, 64)):
-        assert lib.hic_rle_decode_idct_rgb_indexed(*args(H, W)) == _lib.HIC_ERR_ARG, (H, W)
-    assert lib.hic_rle_decode_idct_rgb_indexed(*args(64, 64, stride=3 * 64 - 8)) == _lib.HIC_ERR_ARG
-    assert lib.hic_rle_decode_idct_rgb_indexed(*args(64, 64, stride=3 * 64 + 4)) == _lib.HIC_ERR_ARG
-    assert lib.hic_rle_decode_idct_rgb_indexed(*args(64, 64, cr=ctypes.c_void_p((1 << 20) + 2))) == _lib.HIC_ERR_ARG
-    assert "aligned" in _lib.last_error()
+    for kind in KINDS:
+        fn = getattr(lib, "hic_rle_decode_idct_rgb_" + kind)
+        args = lambda H=64, W=64, cr=P, stride=None, L=P, rpt=1: (  # noqa: E731
+            [L, P, P, P, P] + _rpt(kind, rpt) + [H, W, cr, P, P, 3 * W if stride is None else stride, P, None])
+        _refused(fn, args(L=None), "null pointer")
+        for H, W in ((60, 64), (64, 62), (0, 64)):
+            _refused(fn, args(H, W))
+        _refused(fn, args(stride=3 * 64 - 8))
+        _refused(fn, args(stride=3 * 64 + 4))
+        _refused(fn, args(cr=P + 2), "aligned")
+        _refused(fn, args(L=P + 8), "16-byte aligned")
+        if kind == "slots":
+            _refused(fn, args(rpt=3), "records_per_tile")
+            _refused(fn, args(H=32), "whole records")  # 32 blocks, one record per 64-block tile
 
 
 def test_decode_pair_indexed_arguments():
-    """hic_rle_decode_idct_u8_indexed_pair checks both planes' pointers before any
-    device call."""
+    """hic_rle_decode_idct_u8_indexed_pair / _slots_pair check both planes' pointers,
+    the table and (slots) the record geometry before any device call."""
     lib = _lib.load()
-    p16 = ctypes.c_void_p(1 << 20)  # never dereferenced
-    two = lambda a=p16, b=p16: (ctypes.c_void_p * 2)(a, b)
-    ok = lambda **kw: [kw.get("L", two()), two(), two(), two(), two(), 64, 64, 1, two(), 64, two(), None]
-    assert lib.hic_rle_decode_idct_u8_indexed_pair(*ok(L=two(b=None))) == _lib.HIC_ERR_ARG
-    assert "plane 1: null pointer" in _lib.last_error()
-    assert lib.hic_rle_decode_idct_u8_indexed_pair(*ok(L=two(b=ctypes.c_void_p((1 << 20) + 8)))) == _lib.HIC_ERR_ARG
-    assert "16-byte aligned" in _lib.last_error()
-    bad_table = ok()
-    bad_table[7] = 5
-    assert lib.hic_rle_decode_idct_u8_indexed_pair(*bad_table) == _lib.HIC_ERR_ARG
+    two = lambda a=P, b=P: (ctypes.c_void_p * 2)(a, b)  # noqa: E731
+    for kind in KINDS:
+        fn = getattr(lib, "hic_rle_decode_idct_u8_%s_pair" % kind)
+        ok = lambda L=None, rpt=1, H=64, table=1, status=two(): (  # noqa: E731
+            [L or two(), two(), two(), two(), two()] + _rpt(kind, rpt) + [H, 64, table, two(), 64, status, None])
+        _refused(fn, ok(L=two(b=None)), "plane 1: null pointer")
+        _refused(fn, ok(L=two(b=P + 8)), "16-byte aligned")
+        _refused(fn, ok(table=5))
+        _refused(fn, ok(status=None), "null pointer")
+        if kind == "slots":
+            _refused(fn, ok(rpt=0), "records_per_tile")
+            _refused(fn, ok(H=32), "whole records")
+
+
+def test_decode_plane_indexed_arguments():
+    """hic_rle_decode_idct_u8_indexed / _u8_slots: 64 x 64, chrominance table, pitch 64."""
+    lib = _lib.load()
+    for kind in KINDS:
+        fn = getattr(lib, "hic_rle_decode_idct_u8_" + kind)
+        args = lambda H=64, W=64, table=1, stride=64, V=P, status=P, rpt=1: (  # noqa: E731
+            [P, V, P, P, P] + _rpt(kind, rpt) + [H, W, table, P, stride, status, None])
+        _refused(fn, args(status=None), "null pointer")
+        _refused(fn, args(table=5))
+        _refused(fn, args(stride=56))
+        _refused(fn, args(V=P + 8), "16-byte aligned")
+        _refused(fn, args(H=0))
+        if kind == "slots":
+            _refused(fn, args(rpt=3), "records_per_tile")
+            _refused(fn, args(H=32, W=64, rpt=1), "whole records")   # 32 blocks
+            _refused(fn, args(H=8, W=24, rpt=2), "whole records")    # 3 blocks
+
+
+def test_decode_blocks_indexed_arguments():
+    """hic_rle_decode_i16_indexed / _slots (the block-level indexed decoders)."""
+    lib = _lib.load()
+    big = (1 << 31) // 63
+    slots = lambda nblk=64, rpt=1, blocks=P: [P, P, P, P, nblk, rpt, P, blocks, P, None]  # noqa: E731
+    fn = lib.hic_rle_decode_i16_slots
+    _refused(fn, slots(blocks=None), "null pointer")
+    _refused(fn, slots(nblk=0))
+    _refused(fn, slots(rpt=3), "records_per_tile")
+    _refused(fn, slots(nblk=32), "whole records")
+    _refused(fn, slots(blocks=P + 8), "aligned")
+    _refused(fn, slots(nblk=big + 64))
+    indexed = lambda nblk=64, ix=P, blocks=P: [P, P, P, P, nblk, ix, blocks, P, None]  # noqa: E731
+    fn = lib.hic_rle_decode_i16_indexed
+    _refused(fn, indexed(ix=None), "null pointer")
+    _refused(fn, indexed(nblk=0))
+    _refused(fn, indexed(blocks=P + 8), "aligned")
+    _refused(fn, indexed(nblk=big + 1))
+
+
+def _rle_job(**kw):
+    """A hic_rle_job16 the batch encoders accept (64 blocks, one record per tile, 1 MiB
+    of workspace), with the fields in kw replaced."""
+    f = dict(blocks=P, nblk=64, d_stitch=None, dc_diff=P, sym_len=P, sym_val=P, sym_cap=1 << 20, d_count=P,
+             workspace=P, records_per_tile=1, workspace_bytes=1 << 20, d_index=None)
+    f.update(kw)
+    return _lib.RleJob16(**f)
+
+
+def _jobs(*jobs):
+    return (_lib.RleJob16 * len(jobs))(*jobs)
+
+
+def test_rle_batch_encoders_refuse_bad_jobs():
+    """hic_rle_encode_i16_tiles_batch / _rows_batch check the counts, max_len and every
+    job (pointers, block count, alignment, records per tile, the d_index rule, row
+    lengths, the workspace size) before any device call."""
+    lib = _lib.load()
+    good = _rle_job()
+    tiles = lambda n, jobs, max_len=15: [n, jobs, max_len, None]  # noqa: E731
+    fn = lib.hic_rle_encode_i16_tiles_batch
+    _refused(fn, tiles(0, _jobs(good)))
+    _refused(fn, tiles(9, _jobs(*[good] * 9)))
+    _refused(fn, tiles(1, _jobs(good), max_len=0), "max_len")
+    _refused(fn, tiles(1, _jobs(good), max_len=257), "max_len")
+    for bad in (_rle_job(sym_val=None), _rle_job(nblk=0), _rle_job(blocks=P + 8), _rle_job(records_per_tile=3),
+                _rle_job(d_index=P, d_stitch=P), _rle_job(workspace_bytes=8)):
+        _refused(fn, tiles(2, _jobs(good, bad)), "job 1")
+    _refused(fn, tiles(2, _jobs(good, _rle_job(records_per_tile=3))), "records_per_tile")
+    _refused(fn, tiles(2, _jobs(good, _rle_job(d_index=P, d_stitch=P))), "d_index")
+    rb = lambda *v: (ctypes.c_int64 * len(v))(*v)  # noqa: E731
+    rows = lambda n, jobs, row_blocks, max_len=15: [n, jobs, row_blocks, max_len, None]  # noqa: E731
+    fn = lib.hic_rle_encode_i16_rows_batch
+    _refused(fn, rows(0, _jobs(good), rb(8)))
+    _refused(fn, rows(1, _jobs(good), None))
+    _refused(fn, rows(1, _jobs(good), rb(8), max_len=0), "max_len")
+    for bad in (_rle_job(dc_diff=None), _rle_job(blocks=P + 8), _rle_job(records_per_tile=3),
+                _rle_job(workspace_bytes=0), _rle_job(workspace_bytes=8)):
+        _refused(fn, rows(2, _jobs(good, bad), rb(8, 8)), "job 1")
+    _refused(fn, rows(2, _jobs(good, good), rb(8, 7)), "row_blocks")
+    _refused(fn, rows(1, _jobs(good), rb(0)), "row_blocks")
+    _refused(fn, rows(1, _jobs(_rle_job(d_index=P)), rb(8)), "d_index")
 
 
 def test_knob_defaults_and_ranges():
@@ -171,7 +277,7 @@ def test_knob_defaults_and_ranges():
         assert _lib.get_knob("dct_path") == 0
     for bad in (3, 4, 5, -2):  # 3 / 4: the packed and two-lane kernels, removed in round 5
         assert _lib.load().hic_set_knob(0, bad) == _lib.HIC_ERR_ARG
-    for retired in (9, 10, 11, 12, 14, 15):  # retired knobs: any value but the default is refused
+    for retired in (4, 5, 6, 9, 10, 11, 12, 14, 15):  # retired knobs: any value but the default is refused
         assert _lib.load().hic_set_knob(retired, 0) == _lib.HIC_ERR_ARG
     # resetting every knob to its default works (-1 on a retired knob is a no-op)
     for k in range(16):
