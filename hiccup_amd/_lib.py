@@ -49,6 +49,12 @@ class WireJob(ctypes.Structure):
                 ("rec_src", _vp), ("nrec", _i64), ("pos_shift", _i64), ("rec_dst", _vp), ("d_count", _vp)]
 
 
+class SlotFillJob(ctypes.Structure):
+    """hic_slot_fill_job (include/hiccup_hip.h): one segment of hic_slots_fill_batch."""
+    _fields_ = [("wire", _vp), ("blocks", _vp), ("nblk", _i64), ("block0", _i64), ("channel", _int),
+                ("table_id", _int)]
+
+
 class Encode420Job(ctypes.Structure):
     """hic_encode420_job (include/hiccup_hip.h): one encode of hic_encode420_batch_u8."""
     _fields_ = [("rgb_rows", _vp), ("in_row0", _i64), ("in_rows", _i64), ("H", _i64), ("W", _i64),
@@ -107,6 +113,7 @@ SIGNATURES = {
     "hic_wire_pack_batch": (_int, [_int, _vp, _vp]),
     "hic_wire_unpack_batch": (_int, [_int, _vp, _vp]),
     "hic_wire_flags_apply": (_int, [_int, _vp, _vp]),
+    "hic_slots_fill_batch": (_int, [_int, _vp, _int, _vp, _int, _vp]),
     "hic_encode420_batch_u8": (_int, [_int, _vp, _int, _vp, _vp, _vp]),
     "hic_huffman_decode_batch": (_int, [_int, _vp, _vp]),
     "hic_huffman_from_codes": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),

@@ -94,12 +94,17 @@ __device__ __forceinline__ void slot_symbols_general(const uint32_t (&zw)[32], i
 // wave's stage, still holding every block (this lane's in row `lane`).  SEG: lanes
 // 0-31 hold record A's 32 blocks and 32-63 record B's (the chroma pass, Cr and
 // Cb); else one 64-block record A.  CHECK_WIDE: the luminance table (zig-zag slot 3
-// can need 13 bits).  Every lane must call it.
-template <bool SEG, bool CHECK_WIDE, bool NT = true>
+// can need 13 bits).  Every lane must call it.  OPT_B (SEG only; the fill kernel of
+// wire.hip, whose segment can end in a single 32-block record): with b_absent,
+// record B does not exist -- lanes 32-63 hold all-zero blocks (so B has no
+// symbols to copy out) and write no DC difference, record or last DC.
+template <bool SEG, bool CHECK_WIDE, bool NT = true, bool OPT_B = false>
 __device__ __forceinline__ void slot_pass(const uint32_t (&zw)[32], uint2 *st2, int lane, const SlotRec &A,
-                                          const SlotRec &B) {
+                                          const SlotRec &B, bool b_absent = false) {
+  static_assert(SEG || !OPT_B, "only a two-record pass has a record B");
   const int sl = SEG ? (lane & 31) : lane;
   const bool hi = SEG && lane >= 32;
+  const bool live = !(OPT_B && hi && b_absent);  // (constant true without OPT_B)
   const SlotRec &R = hi ? B : A;
   // ---- 1. the block's summary
   const uint64_t ac = nz_mask16(zw) >> 1;  // bit j = AC j
@@ -112,7 +117,7 @@ __device__ __forceinline__ void slot_pass(const uint32_t (&zw)[32], uint2 *st2, 
   // subtracts the previous record's last DC)
   const int dc = (int)(int16_t)(zw[0] & 0xFFFFu);
   const int dprev = wave_shr1_i32(0, dc);
-  R.dc[sl] = sl == 0 ? dc : dc - dprev;
+  if (live) R.dc[sl] = sl == 0 ? dc : dc - dprev;
   // ---- 2. offsets inside the record (positions relative to its first AC: int32)
   const int lastr = last >= 0 ? sl * 63 + last : -1;
   const int incl = SEG ? seg32_incl_max_i32(lastr) : wave_incl_max_i32(lastr);
@@ -131,8 +136,8 @@ __device__ __forceinline__ void slot_pass(const uint32_t (&zw)[32], uint2 *st2, 
   const int nR = hi ? nB : nA, lR = hi ? lB : lA;
   // the record: its first nonzero's position (head lane, or lane 0 of an empty
   // record), the last one's and the symbols after the first; its last DC
-  if (lR < 0 ? sl == 0 : head) R.rec[0] = lR < 0 ? -1 : R.pos + sl * 63 + first;
-  if (sl == 0) {
+  if (live && (lR < 0 ? sl == 0 : head)) R.rec[0] = lR < 0 ? -1 : R.pos + sl * 63 + first;
+  if (live && sl == 0) {
     R.rec[1] = lR >= 0 ? R.pos + lR : -1;
     R.rec[2] = lR >= 0 ? nR - 1 : 0;
     *R.rdc = hi ? dB : dA;

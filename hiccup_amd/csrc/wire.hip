@@ -17,7 +17,13 @@
 //  hic_rle_records_rebase: a shard's RLE tile records moved into the whole
 //                       image's record array (positions + pos_shift), so the
 //                       gathering rank runs the scan + emit without a tile pass
+//  hic_slots_fill_batch: segments of already-quantized blocks (wire format, or
+//                       int16) straight into a channel's slot layout (slots.h):
+//                       wire -> registers -> slot_pass, no coefficient store and
+//                       no emit; hic_rle_slots_close then closes the whole image
 #include "hic_common.h"
+#include "dct_core.h"  // kStageU2: slot_pass's stage row stride
+#include "slots.h"
 #include "wire_widths.h"
 
 namespace hic {
@@ -95,10 +101,11 @@ __global__ __launch_bounds__(64 * kWPB) void k_wire_pack(const int16_t *__restri
 // unpack: the tile into LDS (coalesced), lane j extracts block j into its stage
 // row, the stage leaves as 1 KiB stores
 constexpr int kRowU4 = 9;  // 144 B stage rows (128 B + pad)
+// tile t of `wire` through the LDS tile st: lane j leaves holding block j as 32
+// packed zig-zag int16 pairs (slot 2 i in the low half of w[i])
 template <int TABLE>
-__device__ __forceinline__ void wire_unpack_tile(const uint32_t *__restrict__ wire, int64_t nblk,
-                                                 int16_t *__restrict__ blocks, int64_t t, int lane, uint32_t *st,
-                                                 uint4 *stage) {
+__device__ __forceinline__ void wire_extract_tile(const uint32_t *__restrict__ wire, int64_t t, int lane,
+                                                  uint32_t *st, uint32_t (&w)[32]) {
   using G = WireGeo<TABLE>;
   const uint4 *src = reinterpret_cast<const uint4 *>(wire + t * G::kStride);
   for (int c = lane; c < G::kStride / 4; c += 64) {
@@ -115,7 +122,6 @@ __device__ __forceinline__ void wire_unpack_tile(const uint32_t *__restrict__ wi
     acc = (uint64_t)st[wi++] >> ph;
     n = 32 - ph;
   }
-  uint32_t w[32];
 #pragma unroll
   for (int i = 0; i < 64; ++i) {
     const int nb = kWireW[TABLE][i];
@@ -132,6 +138,14 @@ __device__ __forceinline__ void wire_unpack_tile(const uint32_t *__restrict__ wi
     else
       w[i >> 1] = (uint32_t)v & 0xFFFFu;
   }
+}
+
+template <int TABLE>
+__device__ __forceinline__ void wire_unpack_tile(const uint32_t *__restrict__ wire, int64_t nblk,
+                                                 int16_t *__restrict__ blocks, int64_t t, int lane, uint32_t *st,
+                                                 uint4 *stage) {
+  uint32_t w[32];
+  wire_extract_tile<TABLE>(wire, t, lane, st, w);
   uint4 *row = stage + lane * kRowU4;
 #pragma unroll
   for (int k = 0; k < 8; ++k) row[k] = make_uint4(w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3]);
@@ -234,6 +248,84 @@ __global__ void k_wire_flags_apply(WireBatch B) {
   if (J.flag && J.count && *J.flag != 0) *J.count = HIC_COUNT_WIRE_OVERFLOW;
 }
 
+// ---- slot fill (hic_slots_fill_batch): the receiving rank of a "slots" gather.
+// Wave t of a launch takes one 64-block tile of one segment: lane j gets block j
+// as 32 packed zig-zag int16 pairs -- from the wire tile by wire_extract_tile, or
+// from int16 blocks by eight 16-byte loads -- puts it in its stage row and runs
+// slot_pass (slots.h), which writes the record's symbols, DC differences, record
+// and last DC exactly as the fused encoder does for the same blocks.  SEG
+// (records_per_tile 2): lanes 0-31 and 32-63 are two consecutive 32-block records
+// of the same channel; a segment's last tile may hold only the first (slot_pass's
+// OPT_B: the absent half writes nothing).  One launch per (table, SEG) takes every
+// such segment of the call through a by-value job table.
+struct FillSegD {
+  const uint32_t *wire;   // the segment in the wire format, or
+  const int16_t *blocks;  // its int16 zig-zag blocks
+  int64_t nblk, block0;
+  int chan;
+};
+struct FillChanD {
+  uint8_t *slen;
+  int16_t *sval;
+  int32_t *dc;
+  int64_t *rec;
+  int32_t *rdc;
+};
+struct FillBatch {
+  FillSegD j[kWireJobsMax];
+  int64_t tile0[kWireJobsMax + 1];
+  FillChanD c[3];
+  int n;
+};
+static_assert(sizeof(FillBatch) <= 4096 - 256, "kernel arguments stay under 4 KiB");
+
+template <int TABLE, bool SEG>
+__global__ __launch_bounds__(64 * kWPB) void k_slots_fill(FillBatch B) {
+  __shared__ uint32_t s_tile[kWPB][kTileLds];
+  __shared__ __attribute__((aligned(16))) uint2 s_stage[kWPB][64 * kStageU2];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int64_t t = (int64_t)blockIdx.x * kWPB + wv;
+  if (t >= B.tile0[B.n]) return;  // wave-uniform
+  int k = 0;
+  while (k + 1 < B.n && t >= B.tile0[k + 1]) ++k;  // wave-uniform
+  const FillSegD &J = B.j[k];
+  const FillChanD &C = B.c[J.chan];
+  const int64_t tt = t - B.tile0[k];
+  const int64_t nvalid = J.nblk - tt * 64;  // >= 64, or 32 in the last tile of a SEG segment
+  uint32_t w[32];
+  if (J.wire) {
+    wire_extract_tile<TABLE>(J.wire, tt, lane, s_tile[wv], w);
+  } else if (lane < nvalid) {
+    const uint4 *q = reinterpret_cast<const uint4 *>(J.blocks + (tt * 64 + lane) * 64);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const uint4 v = q[i];
+      w[4 * i] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w;
+    }
+  }
+  if (lane >= nvalid) {  // the absent half: all-zero blocks, whatever the wire's padding holds
+#pragma unroll
+    for (int i = 0; i < 32; ++i) w[i] = 0;
+  }
+  uint2 *st2 = s_stage[wv];
+  uint2 *row = st2 + lane * kStageU2;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) row[i] = make_uint2(w[2 * i], w[2 * i + 1]);
+  __builtin_amdgcn_wave_barrier();
+  const int64_t b0 = J.block0 + tt * 64;
+  if constexpr (!SEG) {
+    const int64_t r = b0 >> 6;
+    const SlotRec A{C.slen + r * kSlotY, C.sval + r * kSlotY, C.dc + b0, C.rec + r * 3, C.rdc + r, b0 * 63};
+    slot_pass<false, TABLE == 0>(w, st2, lane, A, A);
+  } else {
+    const int64_t r = b0 >> 5;
+    const SlotRec A{C.slen + r * kSlotC, C.sval + r * kSlotC, C.dc + b0, C.rec + r * 3, C.rdc + r, b0 * 63};
+    const SlotRec Bb{C.slen + (r + 1) * kSlotC, C.sval + (r + 1) * kSlotC, C.dc + b0 + 32, C.rec + (r + 1) * 3,
+                     C.rdc + r + 1, (b0 + 32) * 63};
+    slot_pass<true, TABLE == 0, true, true>(w, st2, lane, A, Bb, nvalid < 64);
+  }
+}
+
 }  // namespace
 }  // namespace hic
 
@@ -305,6 +397,70 @@ extern "C" int hic_wire_flags_apply(int n, const hic_wire_job *jobs, void *strea
   if (int e = wire_tables(n, jobs, false, all, tb, maxrec)) return e;
   hipLaunchKernelGGL(k_wire_flags_apply, dim3(1), dim3(64), 0, as_stream(stream), all);
   return check_launch("k_wire_flags_apply");
+}
+
+extern "C" int hic_slots_fill_batch(int nchan, const hic_slot_job *chan, int n, const hic_slot_fill_job *segs,
+                                    int max_len, void *stream) {
+  // every channel and segment is checked before anything launches
+  if (nchan < 1 || nchan > 3 || !chan) return arg_error("1 <= nchan <= 3 channels");
+  if (n < 1 || n > kWireJobsMax || !segs) return arg_error("1 <= n <= %d segments", kWireJobsMax);
+  if (max_len != kSlotM) return arg_error("the slot layout needs max_len 15");
+  FillBatch tb[2][2] = {};  // [table][records_per_tile - 1]
+  FillChanD cd[3] = {};
+  for (int c = 0; c < nchan; ++c) {
+    const hic_slot_job &a = chan[c];
+    if (!a.slot_len || !a.slot_val || !a.dc_diff || !a.workspace) return arg_error("channel %d: null pointer", c);
+    if ((reinterpret_cast<uintptr_t>(a.slot_len) | reinterpret_cast<uintptr_t>(a.slot_val)) % 16)
+      return arg_error("channel %d: slot arrays must be 16-byte aligned", c);
+    if (a.nblk <= 0 || a.nblk > (int64_t)INT32_MAX / 63) return arg_error("channel %d: nblk", c);
+    if (a.records_per_tile != 1 && a.records_per_tile != 2)
+      return arg_error("channel %d: records_per_tile must be 1 or 2", c);
+    if (a.nblk % (64 / a.records_per_tile))
+      return arg_error("channel %d: nblk must be a multiple of %lld (whole records)", c,
+                       (long long)(64 / a.records_per_tile));
+    const int64_t need = (int64_t)hic_rle_slots_workspace_bytes(a.nblk, (int)a.records_per_tile);
+    if (a.workspace_bytes < need)
+      return arg_error("channel %d: workspace of %lld bytes, %lld needed", c, (long long)a.workspace_bytes,
+                       (long long)need);
+    int64_t *rec = static_cast<int64_t *>(a.workspace);
+    cd[c] = FillChanD{a.slot_len, a.slot_val, a.dc_diff, rec,
+                      reinterpret_cast<int32_t *>(rec + slot_rdc_word(slot_nrec(a.nblk, a.records_per_tile)))};
+  }
+  for (int i = 0; i < n; ++i) {
+    const hic_slot_fill_job &J = segs[i];
+    if (J.channel < 0 || J.channel >= nchan) return arg_error("segment %d: channel", i);
+    if (J.table_id != HIC_TABLE_LUMINANCE && J.table_id != HIC_TABLE_CHROMINANCE)
+      return arg_error("segment %d: table", i);
+    if ((J.wire != nullptr) == (J.blocks != nullptr))
+      return arg_error("segment %d: exactly one of wire and blocks", i);
+    if ((reinterpret_cast<uintptr_t>(J.wire) | reinterpret_cast<uintptr_t>(J.blocks)) % 16)
+      return arg_error("segment %d: wire / blocks must be 16-byte aligned", i);
+    const hic_slot_job &a = chan[J.channel];
+    const int64_t bpr = 64 / a.records_per_tile;
+    if (J.nblk <= 0 || J.nblk % bpr || J.block0 < 0 || J.block0 % bpr)
+      return arg_error("segment %d: nblk and block0 must be on record boundaries (%lld blocks)", i, (long long)bpr);
+    if (J.block0 > a.nblk || J.nblk > a.nblk - J.block0)
+      return arg_error("segment %d: blocks [%lld, +%lld) past the channel's %lld", i, (long long)J.block0,
+                       (long long)J.nblk, (long long)a.nblk);
+    FillBatch &T = tb[J.table_id][a.records_per_tile - 1];
+    T.tile0[T.n + 1] = T.tile0[T.n] + (J.nblk + 63) / 64;
+    T.j[T.n++] = FillSegD{reinterpret_cast<const uint32_t *>(J.wire), J.blocks, J.nblk, J.block0, J.channel};
+  }
+  const hipStream_t s = as_stream(stream);
+  for (int tbl = 0; tbl < 2; ++tbl)
+    for (int seg = 0; seg < 2; ++seg) {
+      FillBatch &B = tb[tbl][seg];
+      if (B.n == 0) continue;
+      for (int c = 0; c < 3; ++c) B.c[c] = cd[c];
+      const dim3 grid((unsigned)((B.tile0[B.n] + kWPB - 1) / kWPB)), block(64 * kWPB);
+      auto launch = [&](auto kern) { hipLaunchKernelGGL(kern, grid, block, 0, s, B); };
+      if (tbl == 0)
+        seg ? launch(k_slots_fill<0, true>) : launch(k_slots_fill<0, false>);
+      else
+        seg ? launch(k_slots_fill<1, true>) : launch(k_slots_fill<1, false>);
+      if (int e = check_launch("k_slots_fill")) return e;
+    }
+  return HIC_OK;
 }
 
 extern "C" size_t hic_wire_bytes(int64_t nblk, int table_id) {

@@ -96,6 +96,17 @@ def slots_eligible(H, W, max_len=15, rows=None, out=None, fused=None, landing_rp
             and W % 512 == 0 and H % 16 == 0 and H >= 16 and H * W * 3 <= 2**31 - 1)
 
 
+SLOT_RPT = {"lum": 1, "cr": 2, "cb": 2}  # the slot layout's records per 64-block tile
+
+
+def slot_fill_job(k, block0, nblk, blocks=None, wire=None):
+    """hic_slot_fill_job of channel k: blocks [block0, block0 + nblk) of the channel
+    from `blocks` (int16 zig-zag blocks) or `wire` (hic_wire_pack_i16's format):
+    device tensors or addresses, exactly one of the two."""
+    p = [x.data_ptr() if isinstance(x, torch.Tensor) else x for x in (wire, blocks)]
+    return _lib.SlotFillJob(p[0], p[1], nblk, block0, CHANNELS.index(k), TABLES[k])
+
+
 class SlotIndex:
     """The slot-layout stream of an Encoder for Decoder.decode(index=...): per channel
     the slot arrays, the close's record index and the records per 64-block tile."""
@@ -125,7 +136,10 @@ class Encoder:
         transform, no plane buffers, and the RLE record layout of the shards that
         fill it (their encoder_layout rpt), whatever this shape alone would pick.
         slots: the slot layout (module docstring); None = whenever slots_eligible,
-        False = the coefficient + emit chain."""
+        False = the coefficient + emit chain.  slots=True with landing_rpt = SLOT_RPT
+        is a slot landing zone (a whole image slots_eligible accepts): fill() writes
+        its records from gathered segments, entropy() closes them, and everything
+        after that is a slot encoder's."""
         if H < 2 or W < 2:
             raise ValueError("image must be at least 2 x 2")
         device.require_gpu()
@@ -137,8 +151,13 @@ class Encoder:
         self.want_index = bool(index)
         self.landing = landing_rpt is not None
         ok = slots_eligible(H, W, max_len, rows, out, fused, landing_rpt)
+        if slots and self.landing:
+            # a slot landing zone (hic_slots_fill_batch fills it, fill()): the shape rule
+            # of a whole-image slot encoder, and the slot layout's records
+            ok = slots_eligible(H, W, max_len, rows, out, fused) and dict(landing_rpt) == SLOT_RPT
         if slots and not ok:
-            raise ValueError("the slot layout needs a whole image with W % 512 == 0, H % 16 == 0 and max_len 15")
+            raise ValueError("the slot layout needs a whole image with W % 512 == 0, H % 16 == 0 and max_len 15"
+                             + (" (a landing zone: landing_rpt %r)" % (SLOT_RPT,) if self.landing else ""))
         self.slots = ok if slots is None else bool(slots)
         if self.landing:
             self.fused, self.rpt = False, dict(landing_rpt)
@@ -280,6 +299,22 @@ class Encoder:
                                    self.ws[k].data_ptr(), self.ws_bytes[k], self.counts[i:i + 1].data_ptr(),
                                    self.sym_len[k].data_ptr(), self.sym_val[k].data_ptr(), self.cap[k])
         return jobs
+
+    def fill(self, segs, stream=None):
+        """Slot layout: segments of already-quantized blocks into their records' slots
+        (hic_slots_fill_batch; what transform() writes for those records).  segs: a
+        list of slot_fill_job(...) (32 per call), or a ready _lib.SlotFillJob array.
+        entropy() closes the image once every record is filled."""
+        if not self.slots:
+            raise ValueError("fill() needs a slot-layout encoder")
+        s = device.stream_ptr(stream)
+        if isinstance(segs, ctypes.Array):
+            segs = [segs]
+        else:
+            segs = [(_lib.SlotFillJob * len(segs[i:i + 32]))(*segs[i:i + 32]) for i in range(0, len(segs), 32)]
+        jobs = self._slot_jobs()
+        for arr in segs:
+            _lib.call("hic_slots_fill_batch", 3, jobs, len(arr), arr, self.max_len, s)
 
     def compact(self, stream=None):
         """Slot layout: the contiguous symbol stream into sym_len / sym_val (what the

@@ -133,6 +133,35 @@ def records_aligned(ranges, rpt):
     return all((b0 * rpt[k]) % 64 == 0 for k in CHANNELS for b0, _ in ranges[k])
 
 
+WIRE_KINDS = ("stream", "slots")  # the gather kinds whose shards travel in the wire format
+
+
+def _slots_gather_refusal(H, W, world, max_len=15):
+    """None when a "slots" gather can take this shape, else the condition it misses."""
+    if max_len != 15:
+        return "max_len must be 15 (4-bit symbol lengths in the slot layout)"
+    if W % 512:
+        return "W %% 512 == 0 (W = %d)" % W
+    if H % 16:
+        return "H %% 16 == 0 (H = %d)" % H
+    if H // 16 < world:
+        return "at least 16 rows per rank (%d rows, %d ranks)" % (H, world)
+    if not pipeline.slots_eligible(H, W, max_len):
+        return "a whole image the slot layout takes (< 2 GiB of RGB)"
+    if not all(pipeline.encoder_layout(H, W, rr)[0] for rr in plan(H, world)):
+        return "shards the fused kernel takes"
+    return None
+
+
+def slots_gather_eligible(H, W, world, max_len=15):
+    """Whether ShardEncoder(gather_kind="slots") takes this shape: W % 512 == 0, H %
+    16 == 0, max_len 15 and at least 16 rows per rank -- every shard (a multiple of
+    16 rows) then starts and ends on record boundaries of all three planes (2 W / 8
+    luminance blocks = whole 64-block records, W / 16 chroma blocks = whole 32-block
+    records per 16 rows) -- a whole image the slot layout takes and fused shards."""
+    return _slots_gather_refusal(H, W, world, max_len) is None
+
+
 class ShardEncoder:
     """One rank's part of a tile-sharded encode of an H x W RGB image.
 
@@ -146,16 +175,29 @@ class ShardEncoder:
     records to gather_to, which unpacks them and runs the scan + emit of the whole
     image -- codec.jpeg_encode's single stream (codec.py:55-99,286-301) ends on
     gather_to (self.whole.sym_len / sym_val / dc / counts), with no host sync and
-    no per-shard entropy pass.  See stream_item / pack / finish."""
+    no per-shard entropy pass.  See stream_item / pack / finish.
+    gather_kind "slots": as "stream", but the stream ends on gather_to in the slot
+    layout: the ranks ship their blocks only (no records), and gather_to fills
+    the slots of a landing zone (pipeline.Encoder(landing_rpt=SLOT_RPT, slots=True))
+    straight from the wire segments and its own blocks (hic_slots_fill_batch: no
+    int16 unpack, no emit), then closes it (hic_rle_slots_close): self.whole has
+    a SlotIndex, hic_image(from_slots=True) and the slot decoders.  Only for shapes
+    slots_gather_eligible accepts (ValueError otherwise: there is no fallback)."""
 
     def __init__(self, H, W, rank=None, world=None, group=None, max_len=15, gather_to=None, fused=None,
                  gather_kind="blocks"):
-        if gather_kind not in ("blocks", "stream"):
-            raise ValueError("gather_kind must be 'blocks' or 'stream'")
-        if gather_kind == "stream" and gather_to is None:
-            raise ValueError("gather_kind 'stream' needs gather_to")
+        if gather_kind not in ("blocks",) + WIRE_KINDS:
+            raise ValueError("gather_kind must be 'blocks', 'stream' or 'slots'")
+        if gather_kind in WIRE_KINDS and gather_to is None:
+            raise ValueError("gather_kind '%s' needs gather_to" % gather_kind)
         self.rank = dist.get_rank(group) if rank is None else rank
         self.world = dist.get_world_size(group) if world is None else world
+        if gather_kind == "slots":
+            why = _slots_gather_refusal(H, W, self.world, max_len)
+            if why is None and fused is not None and not fused:
+                why = "fused shards (fused=False was given)"
+            if why is not None:
+                raise ValueError("gather_kind 'slots' needs " + why)
         self.group = group
         self.H, self.W = H, W
         self.rows = plan(H, self.world)[self.rank]
@@ -168,7 +210,11 @@ class ShardEncoder:
             fused = all(pipeline.encoder_layout(H, W, rr)[0] for rr in plan(H, self.world))
         self.whole = None
         out = None
-        if gather_to is not None and self.rank == gather_to:
+        if gather_to is not None and self.rank == gather_to and gather_kind == "slots":
+            # the slot landing zone: no whole-image coefficients exist, this rank's
+            # encoder keeps its own buffers and finish() fills its records from them
+            self.whole = pipeline.Encoder(H, W, max_len=max_len, landing_rpt=pipeline.SLOT_RPT, slots=True)
+        elif gather_to is not None and self.rank == gather_to:
             if gather_kind == "stream":
                 # the whole image's entropy stage lives here: its buffers are the
                 # landing zone, this rank's encoder writes its slice in place.  Its
@@ -193,8 +239,9 @@ class ShardEncoder:
         self.all_summ = device.zeros((self.world, 3, 4), torch.int64)
         self.stitch = device.zeros((3, 4), torch.int64)
         self.all_counts = device.zeros((self.world, 3), torch.int64)
-        if gather_kind == "stream":
-            self.records = records_aligned(self.ranges, self.enc.rpt)
+        if gather_kind in WIRE_KINDS:
+            # ("slots": blocks only -- the receiver derives the records itself)
+            self.records = gather_kind == "stream" and records_aligned(self.ranges, self.enc.rpt)
             self.wranges = wire_ranges(self.ranges, self.enc.rpt, self.records)
             if self.rank == gather_to:
                 self.wire_full = {k: device.empty((self.wranges[k][-1][1],), torch.uint8) for k in CHANNELS}
@@ -217,11 +264,12 @@ class ShardEncoder:
     @property
     def wire_bytes(self):
         """Bytes of one image on the wire (every rank's segments, all channels)."""
-        return sum(self.wranges[k][-1][1] for k in CHANNELS) if self.gather_kind == "stream" else None
+        return sum(self.wranges[k][-1][1] for k in CHANNELS) if self.gather_kind in WIRE_KINDS else None
 
     def pack(self, stream=None):
-        """gather_kind "stream", a rank other than gather_to: this rank's blocks into
-        the wire format and its tile records, rebased, behind them (on `stream`)."""
+        """gather_kind "stream" / "slots", a rank other than gather_to: this rank's blocks
+        into the wire format and ("stream") its tile records, rebased, behind them (on
+        `stream`)."""
         wire_batch("hic_wire_pack_batch", self.pack_jobs(), stream)
 
     def pack_jobs(self):
@@ -261,14 +309,24 @@ class ShardEncoder:
         """gather_to, after the wire gather: every other rank's blocks unpacked into
         the whole image, the tile records placed (or, when the shards do not start
         on record boundaries, recomputed by a tile pass), then the whole image's
-        scan + emit (one stream, no stitch).  On `stream`."""
+        scan + emit (one stream, no stitch).  gather_kind "slots": every rank's
+        records filled into the landing zone's slots -- the peers' from their wire
+        segments, this rank's from its own blocks -- in one hic_slots_fill_batch call,
+        then the close.  On `stream`, no host sync."""
         s = device.stream_ptr(stream)
         whole = self.whole
         if whole.rpt != self.enc.rpt:
             raise RuntimeError("landing zone record layout %r != the shards' %r" % (whole.rpt, self.enc.rpt))
         if getattr(self, "_finish_jobs", None) is None:  # fixed buffers: built once
-            self._finish_jobs = self._make_finish_jobs()
+            self._finish_jobs = (self._make_fill_jobs() if self.gather_kind == "slots"
+                                 else self._make_finish_jobs())
         jobs, flags = self._finish_jobs
+        if self.gather_kind == "slots":
+            whole.fill(jobs, stream)
+            whole.entropy(stream)  # the close
+            if flags:
+                _lib.call("hic_wire_flags_apply", len(flags), flags, s)
+            return
         if jobs:
             _lib.call("hic_wire_unpack_batch", len(jobs), jobs, s)
         if not self.records:
@@ -311,6 +369,27 @@ class ShardEncoder:
         if len(jobs) > 32 or len(flags) > 32:
             raise ValueError("world %d: more than 32 wire segments per image" % self.world)
         return ((_lib.WireJob * len(jobs))(*jobs) if jobs else None,
+                (_lib.WireJob * len(flags))(*flags) if flags else None)
+
+    def _make_fill_jobs(self):
+        """finish()'s batches of a "slots" gather as ctypes arrays: one
+        hic_slot_fill_job per channel and rank (the peers' wire segments, this rank's
+        own int16 blocks), and the senders' flags -> counts."""
+        whole = self.whole
+        jobs, flags = [], []
+        for c, k in enumerate(CHANNELS):
+            for r in range(self.world):
+                b0, b1 = self.ranges[k][r]
+                if r == self.rank:
+                    jobs.append(pipeline.slot_fill_job(k, b0, b1 - b0, blocks=self.enc.coef[k]))
+                    continue
+                o0, o1 = self.wranges[k][r]
+                jobs.append(pipeline.slot_fill_job(k, b0, b1 - b0, wire=self.wire_full[k].data_ptr() + o0))
+                flags.append(_lib.WireJob(None, None, 0, TABLE_OF[k], self.wire_full[k].data_ptr() + o1 - TRAILER_BYTES,
+                                          None, 0, 0, None, whole.counts.data_ptr() + 8 * c))
+        if len(jobs) > 32:
+            raise ValueError("world %d: more than 32 wire segments per image" % self.world)
+        return ((_lib.SlotFillJob * len(jobs))(*jobs),
                 (_lib.WireJob * len(flags))(*flags) if flags else None)
 
     @property
@@ -394,7 +473,7 @@ def _encode_group(encoders, rgb_rows_list, stream, dct_events):
     # the group's shard transforms in one launch (pipeline.transform_batch)
     pipeline.transform_batch([se.enc for se in encoders], rgb_rows_list, stream,
                              in_row0s=[se.span[0] for se in encoders], dct_events=dct_events)
-    if all(se.gather_kind == "stream" for se in encoders):
+    if all(se.gather_kind in WIRE_KINDS for se in encoders):
         return  # the entropy stage runs on the gathering rank (gather_streams_group)
     summs = []
     for se in encoders:
@@ -426,9 +505,10 @@ def gather_coefficients_group(encoders, group=None):
 
 
 def gather_streams_group(encoders, group=None, rccl=None, stream=None):
-    """gather_kind "stream": the wire gathers of several images (image j to rank j)
-    in ONE grouped batch, then each receiving rank's unpack + scan + emit, all on
-    `stream` (default: the current one) with no host sync.  rccl: a RcclGather to
+    """gather_kind "stream" / "slots": the wire gathers of several images (image j to
+    rank j) in ONE grouped batch, then each receiving rank's unpack + scan + emit
+    ("slots": slot fill + close, ShardEncoder.finish), all on `stream` (default: the
+    current one) with no host sync.  rccl: a RcclGather to
     move the bytes through the C-ABI instead of torch.distributed.  Returns each
     encoder's whole-image pipeline.Encoder (its stream) on its gather_to rank, None
     elsewhere."""

@@ -665,6 +665,30 @@ int hic_wire_pack_batch(int n, const hic_wire_job *jobs, void *stream);
 int hic_wire_unpack_batch(int n, const hic_wire_job *jobs, void *stream);
 int hic_wire_flags_apply(int n, const hic_wire_job *jobs, void *stream);
 int hic_rle_records_rebase(const int64_t *d_src, int64_t nrec, int64_t pos_shift, int64_t *d_dst, void *stream);
+/* hic_slots_fill_batch (round 9): segments of blocks that are already quantized --
+ * a gathered shard in the wire format, or int16 zig-zag blocks -- straight into
+ * the slot layout (hic_slot_job above), with no int16 store and no emit: the
+ * receiving rank of a multi-GPU gather (sharding.ShardEncoder, gather_kind "slots").
+ * For the records [block0, block0 + nblk) of chan[channel] it writes exactly what
+ * hic_encode420_slots_u8 writes for them: each record's symbols in its slot (the
+ * first symbol's length as 0), the DC differences (the record's first block keeping
+ * its raw DC), the record and its last DC in the workspace; stream positions are
+ * the whole image's (block0 * 63 onwards).  Once every segment of a channel is
+ * filled, hic_rle_slots_close makes it decodable.  Values must fit the table's wire
+ * widths (tools/check/wire_widths.py; what the encoder's DCT produces does).
+ * nchan <= 3, n <= 32, max_len 15; every channel (pointers, 16-byte aligned slot
+ * arrays, whole records, workspace_bytes) and segment is checked before the first
+ * launch (HIC_ERR_ARG); one launch per (table, records_per_tile) present. */
+typedef struct {
+  const uint8_t *wire;    /* the segment in hic_wire_pack_i16's format, 16-byte aligned, or NULL */
+  const int16_t *blocks;  /* or: int16 zig-zag blocks [nblk][64], 16-byte aligned; exactly one of the two */
+  int64_t nblk;           /* blocks of the segment: > 0, whole records (a multiple of 64 / records_per_tile) */
+  int64_t block0;         /* its first block in the channel's raster block order: a record boundary */
+  int channel;            /* index into the hic_slot_job array passed alongside */
+  int table_id;           /* HIC_TABLE_LUMINANCE / HIC_TABLE_CHROMINANCE: the wire widths */
+} hic_slot_fill_job;
+int hic_slots_fill_batch(int nchan, const hic_slot_job *chan, int n, const hic_slot_fill_job *segs,
+                         int max_len, void *stream);
 
 /* ---- Multi-GPU gather over RCCL (SURVEY.md section 8(b) hic_gather_*; the
  *      whole-image buffers it reassembles are what codec.jpeg_encode consumes,
