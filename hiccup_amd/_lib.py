@@ -75,6 +75,15 @@ class DctPlaneJob(ctypes.Structure):
                 ("rle_workspace", _vp)]
 
 
+class Window(ctypes.Structure):
+    """hic_window (include/hiccup_hip.h): hic_window_plan's geometry of a region decode."""
+    _fields_ = [("Y0", _i64), ("X0", _i64), ("Y1", _i64), ("X1", _i64), ("cy0", _i64), ("cx0", _i64), ("ch", _i64),
+                ("cw", _i64)]
+
+
+STREAM_INDEXED = 0
+STREAM_SLOTS = 1
+
 SIGNATURES = {
     "hic_abi_version": (_int, []),
     "hic_last_error": (_int, [ctypes.c_char_p, _sz]),
@@ -140,6 +149,13 @@ SIGNATURES = {
                                                  _vp]),
     "hic_rle_decode_idct_rgb_slots": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _i64, _i64, _vp, _vp, _vp, _i64, _vp,
                                              _vp]),
+    "hic_rle_stream_index_workspace_bytes": (_sz, [_i64, _i64]),
+    "hic_rle_stream_index_i16": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "hic_window_plan": (_int, [_i64, _i64, _i64, _i64, _i64, _i64, ctypes.POINTER(Window)]),
+    "hic_rle_decode_idct_u8_window_pair": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _int, _i64, _i64,
+                                                  ctypes.POINTER(Window), _vp, _i64, _vp, _vp]),
+    "hic_rle_decode_idct_rgb_window": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _int, _i64, _i64, ctypes.POINTER(Window),
+                                              _vp, _vp, _i64, _vp, _i64, _vp, _vp]),
     "hic_event_create": (_int, [_vp]),
     "hic_event_destroy": (_int, [_vp]),
     "hic_event_elapsed_ms": (_int, [_vp, _vp, _vp]),

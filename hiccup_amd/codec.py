@@ -484,32 +484,49 @@ def decode(hic_image):
 def _decode(hic_image):
     from . import compression, pipeline
 
-    def chained():
-        return compression.jpeg_decompression(_jpeg_decode(hic_image))
+    fast = _fast_streams(hic_image)
+    if fast is not None:
+        H, W, sym_len, sym_val, counts, dc = fast
+        dec = pipeline.Decoder(H, W)
+        rgb = dec.decode(sym_len, sym_val, counts, dc)
+        try:
+            dec.check_status()
+        except ValueError:
+            fast = None
+        if fast is not None:
+            return device.to_host(rgb)
+    return compression.jpeg_decompression(_jpeg_decode(hic_image))
 
+
+def _fast_streams(hic_image):
+    """decode's fast path up to the symbols: (H, W, sym_len, sym_val, counts, dc) --
+    the three channels' uint8 / int16 symbols and int32 DC differences on the device,
+    Huffman-decoded and range-checked -- or None for anything decode hands to the
+    chained calls (its docstring lists them)."""
+    from . import pipeline
     p = hic_image.payloads
     if settings.JPEG_BLOCK_SIZE != 8 or hic_image.hic_type != model.Compression.JPEG or len(p) != 20:
-        return chained()
+        return None
     trees = [huffman.FlatCodes.from_table([q.numbers for q in p[i].payloads]) for i in range(9)]
     if any(t is None for t in trees):
-        return chained()
+        return None
     try:
         (H, W), (h, w) = (tuple(int(v) for v in p[i].numbers) for i in (18, 19))
     except (TypeError, ValueError):
-        return chained()
+        return None
     if H < 2 or W < 2 or (h, w) != (H // 2, W // 2) or (H, W) != tuple(p[18].numbers) or (h, w) != tuple(p[19].numbers):
-        return chained()
+        return None
     if H % 16 or W % 16:
         # a plane that is not whole 8 x 8 blocks: jpeg_decode's length assertions
         # (codec.py:418) are evaluated on the symbols themselves there
-        return chained()
+        return None
     streams = _huffman_streams_device([p[9 + i] for i in range(9)], trees)
     sym_len, sym_val, dc, counts, lims = {}, {}, {}, [], []
     for c, k in enumerate(pipeline.CHANNELS):
         (D, nd), (V, nv), (L, nl) = streams[c], streams[3 + c], streams[6 + c]
         nblk = pipeline._nblk(*((H, W) if k == "lum" else (h, w)))
         if nd != nblk or nv != nl or nv < 1:
-            return chained()
+            return None
         D, V, L = D[:nd], V[:nv], L[:nl]
         # >= 0 when in range: lengths 0..255, values int16, the running DC within +-32767
         lims += [L.min().long(), 255 - L.max().long(), V.min().long() + 32768, 32767 - V.max().long(),
@@ -517,14 +534,81 @@ def _decode(hic_image):
         sym_len[k], sym_val[k], dc[k] = L.to(torch.uint8), V.to(torch.int16), D.contiguous()
         counts.append(nv)
     if int(torch.stack(lims).min().cpu()) < 0:  # one read for the fifteen range checks
-        return chained()
-    dec = pipeline.Decoder(H, W)
-    rgb = dec.decode(sym_len, sym_val, counts, dc)
-    try:
-        dec.check_status()
-    except ValueError:
-        return chained()
-    return device.to_host(rgb)
+        return None
+    return H, W, sym_len, sym_val, counts, dc
+
+
+class OpenImage:
+    """A .hic opened for region decode (codec.open): its symbols, DC differences and a
+    tile index built from them (pipeline.stream_index) stay on the device, and each
+    decode_region decodes only the tiles its window touches (pipeline.RegionDecoder).
+    A file decode's fast path refuses is decoded whole once and served by crops."""
+
+    def __init__(self, hic_image):
+        from . import pipeline
+        self._full = self._streams = self._rdec = None
+        fast = _fast_streams(hic_image)
+        if fast is not None:
+            H, W, sym_len, sym_val, counts, dc = fast
+            index, status = pipeline.stream_index(sym_len, sym_val, counts, dc, H, W)
+            want = [pipeline._nblk(H, W) * 63] + [pipeline._nblk(H // 2, W // 2) * 63] * 2
+            if status.cpu().tolist() == want:  # Decoder.check_status's test, once for the file
+                self._streams = (sym_len, sym_val, device.to_device(np.asarray(counts, np.int64)), dc, index)
+                self.shape = (H, W, 3)
+                return
+        with _gc_paused():
+            self._full = _decode(hic_image)
+        self.shape = tuple(self._full.shape)
+
+    def _check(self, y0, x0, h, w):
+        H, W = self.shape[:2]
+        if min(h, w) < 1 or y0 < 0 or x0 < 0 or y0 + h > H or x0 + w > W:
+            raise ValueError("window (%d, %d, %d, %d) outside the %d x %d image" % (y0, x0, h, w, H, W))
+
+    def decode_region_device(self, y0, x0, h, w):
+        """Rows [y0, y0 + h) x columns [x0, x0 + w) as an (h, w, 3) uint8 device tensor: a
+        view of this object's window buffer, valid until its next decode."""
+        from . import pipeline
+        self._check(y0, x0, h, w)
+        if self._streams is None:
+            return device.to_device(np.ascontiguousarray(self._full[y0:y0 + h, x0:x0 + w]))
+        H, W = self.shape[:2]
+        r = self._rdec
+        if r is None or h > r.max_h or w > r.max_w:
+            r = self._rdec = pipeline.RegionDecoder(H, W, max(h, r.max_h if r else 0), max(w, r.max_w if r else 0))
+        return r.decode(y0, x0, h, w, *self._streams)
+
+    def decode_region(self, y0, x0, h, w):
+        """== decode()[y0:y0 + h, x0:x0 + w], a numpy array."""
+        self._check(y0, x0, h, w)
+        if self._streams is None:
+            return self._full[y0:y0 + h, x0:x0 + w].copy()
+        return device.to_host(self.decode_region_device(y0, x0, h, w).contiguous())
+
+    def decode(self):
+        """The whole image, == codec.decode of the file."""
+        from . import pipeline
+        if self._streams is None:
+            return self._full.copy()
+        H, W = self.shape[:2]
+        sym_len, sym_val, counts, dc, index = self._streams
+        return device.to_host(pipeline.Decoder(H, W).decode(sym_len, sym_val, counts, dc, index=index))
+
+
+def open(hic_image):  # noqa: A001 -- codec.open, as the module's users spell it
+    """A HicImage opened for region decode: everything decode does up to the symbols
+    (the same validation and range checks), then a tile index from the bare streams
+    and one status check; see OpenImage."""
+    with _gc_paused():
+        return OpenImage(hic_image)
+
+
+def decode_region(hic_image, y0, x0, h, w):
+    """== decode(hic_image)[y0:y0 + h, x0:x0 + w] (the definition: anything the fast path
+    refuses -- shapes that are not multiples of 16, a stream decode hands to the
+    chained calls, a block size other than 8 -- is decoded whole and cropped).  A
+    window outside the image raises ValueError."""
+    return open(hic_image).decode_region(y0, x0, h, w)
 
 
 # ------------------------------------------------------------------ out of scope

@@ -24,6 +24,8 @@
 //    numpy does.  The guard is > 10^3 x the reciprocal's error bound.
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "color_core.h"
 #include "dct_core.h"
 #include "rle_core.h"
@@ -307,9 +309,34 @@ constexpr int kRowI16 = 68;  // LDS block row: 64 slots + pad (136 B, conflict-f
 // dword load per row; reflect-101 at the top / left border, replicate at the
 // bottom / right, as pyr_up_at.  Every lane of the wave must take part (the DPP
 // reads); `live` gates the stores.
+//
+// The window form (WIN, geometry g: hic_window as the launcher checked it).  bi, bj,
+// nbx, nby stay IMAGE coordinates, so the border rules do not move: reflect-101 at
+// image row / column 0, replicate at the last; a window edge that is no image edge
+// reads the chroma halo the window planes hold.  Only the addresses become
+// window-relative: cr / cb are the window's chroma planes (chroma rows from g.cy0,
+// columns from g.cx0, g.ch x g.cw samples, pitch g.cpitch), rgb the window's pixels
+// (origin g.oy, g.ox).  All 64 lanes still run (the DPP reads), also those whose block
+// lies outside the window: their chroma addresses are clamped into the window planes
+// (a no-op for a block inside the window and for its left / right neighbour, whose
+// columns the span holds by construction) and their stores are gated: a lane stores
+// only a block of the wave's own block row wbi inside columns [g.bj0, g.bj1).
+struct NoWin {};
+struct WinGeo {
+  int bi0, nrows, bj0, bj1;  // the launch plane's block rows [bi0, bi0 + nrows), columns [bj0, bj1)
+  int tpr;                   // waves per block row (the most tiles a row's columns touch)
+  int oy, ox;                // the plane coordinates of out's first sample
+  int cy0, cx0, ch, cw;      // RGB form: the chroma planes' span
+  int cpitch;
+  int64_t n_ac;              // *d_status of a good launch: 63 per block of the window
+};
+template <bool WIN>
+using WinArg = std::conditional_t<WIN, WinGeo, NoWin>;
+template <bool WIN = false>
 __device__ __forceinline__ void colour_block(const uint32_t (&px)[16], int bi, int bj, int nbx, int nby, int lane,
                                              bool live, const uint8_t *__restrict__ cr, const uint8_t *__restrict__ cb,
-                                             uint8_t *__restrict__ rgb, int64_t rgb_stride) {
+                                             uint8_t *__restrict__ rgb, int64_t rgb_stride,
+                                             const WinArg<WIN> &g = WinArg<WIN>{}, int wbi = 0) {
   const int w = 4 * nbx, h = 4 * nby;
   // The packed pixels are opaque: otherwise the compiler forwards each truncated
   // pixel past its packing to the byte extracts below, and 64 live values instead
@@ -322,19 +349,41 @@ __device__ __forceinline__ void colour_block(const uint32_t (&px)[16], int bi, i
     asm volatile("" : "+v"(y[k]));
   }
   asm volatile("" : "+v"(bi), "+v"(bj) : "v"(y[15]));
+  if constexpr (WIN) live = live && bi == wbi && bj >= g.bj0 && bj < g.bj1;
   // chroma rows 4bi-1 .. 4bi+4: its own four columns, and the wave-end lanes' outer
   // neighbour column (lane 0: the dword left of its own, lane 63: the one right)
   const int ce = lane == 0 ? (bj > 0 ? 4 * bj - 4 : 4 * bj) : (bj < nbx - 1 ? 4 * bj + 4 : 4 * bj);
   uint32_t dcr[6], dcb[6], ecr[6], ecb[6];
+  if constexpr (WIN) {
+    // window-relative dword columns, clamped into the planes (lanes outside the window)
+    auto col = [&](int c) {
+      c -= g.cx0;
+      return c < 0 ? 0 : (c > g.cw - 4 ? g.cw - 4 : c);
+    };
+    const int c0 = col(4 * bj), c1 = col(ce);
 #pragma unroll
-  for (int r = 0; r < 6; ++r) {
-    int s = 4 * bi - 1 + r;
-    s = s < 0 ? 1 : (s >= h ? h - 1 : s);
-    const int64_t ro = (int64_t)s * w;
-    dcr[r] = *reinterpret_cast<const uint32_t *>(cr + ro + 4 * bj);
-    dcb[r] = *reinterpret_cast<const uint32_t *>(cb + ro + 4 * bj);
-    ecr[r] = *reinterpret_cast<const uint32_t *>(cr + ro + ce);
-    ecb[r] = *reinterpret_cast<const uint32_t *>(cb + ro + ce);
+    for (int r = 0; r < 6; ++r) {
+      int s = 4 * bi - 1 + r;
+      s = s < 0 ? 1 : (s >= h ? h - 1 : s);  // the image's border rule, then the window's origin
+      s -= g.cy0;
+      s = s < 0 ? 0 : (s > g.ch - 1 ? g.ch - 1 : s);
+      const int ro = s * g.cpitch;  // (the launcher keeps ch * cpitch < 2^31)
+      dcr[r] = *reinterpret_cast<const uint32_t *>(cr + ro + c0);
+      dcb[r] = *reinterpret_cast<const uint32_t *>(cb + ro + c0);
+      ecr[r] = *reinterpret_cast<const uint32_t *>(cr + ro + c1);
+      ecb[r] = *reinterpret_cast<const uint32_t *>(cb + ro + c1);
+    }
+  } else {
+#pragma unroll
+    for (int r = 0; r < 6; ++r) {
+      int s = 4 * bi - 1 + r;
+      s = s < 0 ? 1 : (s >= h ? h - 1 : s);
+      const int64_t ro = (int64_t)s * w;
+      dcr[r] = *reinterpret_cast<const uint32_t *>(cr + ro + 4 * bj);
+      dcb[r] = *reinterpret_cast<const uint32_t *>(cb + ro + 4 * bj);
+      ecr[r] = *reinterpret_cast<const uint32_t *>(cr + ro + ce);
+      ecb[r] = *reinterpret_cast<const uint32_t *>(cb + ro + ce);
+    }
   }
   // KB: -1020 per half; K4 opaque (a splat 4 is strength-reduced to a shift + add)
   const uint32_t K4 = sreg(0x00040004u), K6 = 0x00060006u, KB = 0xFC04FC04u;
@@ -380,7 +429,9 @@ __device__ __forceinline__ void colour_block(const uint32_t (&px)[16], int bi, i
       }
     }
     if (live) {
-      uint2 *d = reinterpret_cast<uint2 *>(rgb + (int64_t)(8 * bi + r8) * rgb_stride + 24 * bj);
+      int oy = 0, ox = 0;
+      if constexpr (WIN) oy = g.oy, ox = g.ox;
+      uint2 *d = reinterpret_cast<uint2 *>(rgb + (int64_t)(8 * bi + r8 - oy) * rgb_stride + (24 * bj - 3 * ox));
       d[0] = make_uint2(o[0], o[1]);
       d[1] = make_uint2(o[2], o[3]);
       d[2] = make_uint2(o[4], o[5]);
@@ -426,7 +477,22 @@ struct DecPlane {
 };
 // SLOTS: the symbols in the slot layout (slots.h), `index` the close's int32 record
 // index, rsh = log2 records per 64-block tile.
-template <int TABLE, bool FAST, bool RGB = false, bool SLOTS = false>
+// WIN: the window form (hic_rle_decode_idct_*_window).  The launch covers the blocks
+// rows [wg.bi0, wg.bi0 + wg.nrows) x columns [wg.bj0, wg.bj1) of the plane, whole
+// blocks, and `out` is a buffer of just those samples (origin wg.oy, wg.ox).  Waves
+// are enumerated per block row: wg.tpr waves for row bi, wave k of them decoding tile
+// floor((bi * nbx + bj0) / 64) + k while that is <= floor((bi * nbx + bj1 - 1) / 64).
+// When nbx % 64 != 0 a tile wraps over two block rows and is decoded once per row it
+// touches; each decode stores only the blocks of its own row inside the columns, so
+// nothing outside the window's buffer is written and no block is written twice.
+//  * A tile's carried zero run can start arbitrarily far before the window: the index
+//    entry hands its start to the gather, which reads the tile's own symbols only
+//    (index[3t], index[3(t + 1)] bound them), as in the whole-plane form.
+//  * *d_status: the first wave of each plane writes -1 when *d_nsym < 1 and then no
+//    wave decodes or stores anything; otherwise wg.n_ac (63 per block of the window).
+//    No wave of a window launch writes the whole-stream completeness value: a window
+//    does not see the whole stream.
+template <int TABLE, bool FAST, bool RGB = false, bool SLOTS = false, bool WIN = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HIC_DEC_WPE))) void k_rld_idct_indexed(const uint8_t *__restrict__ sym_len_a,
                                                           const int16_t *__restrict__ sym_val_a,
                                                           const int64_t *__restrict__ d_nsym_a,
@@ -436,18 +502,42 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HIC_DEC_WPE
                                                           int64_t *__restrict__ d_status_a,
                                                           const uint8_t *__restrict__ cr = nullptr,
                                                           const uint8_t *__restrict__ cb = nullptr,
-                                                          DecPlane second = DecPlane{}, int rsh = 0) {
+                                                          DecPlane second = DecPlane{}, int rsh = 0,
+                                                          WinArg<WIN> wg = WinArg<WIN>{}) {
   static_assert(!RGB || (TABLE == 0 && FAST), "the RGB form decodes whole-block luma planes");
+  static_assert(!WIN || FAST, "a window holds whole blocks");
   __shared__ uint2 s_tile[4][64 * kRowI16 / 4];
   const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int64_t ntiles = (nblk + 63) / 64;
   int64_t t = (int64_t)blockIdx.x * 4 + wv;
-  const bool b = !RGB && t >= ntiles;  // wave-uniform: the second plane's tile t - ntiles
-  if (b) {
-    if (!second.sym_len || t >= 2 * ntiles) return;
-    t -= ntiles;
-  } else if (t >= ntiles) {
-    return;
+  int wbi = 0;          // WIN: the block row whose blocks this wave stores
+  bool wsecond = false, wfirst = false;
+  if constexpr (WIN) {
+    // every quantity here is wave-uniform (scalar)
+    int g = (int)t;
+    const int nw = wg.nrows * wg.tpr;
+    wsecond = !RGB && g >= nw;
+    if (wsecond) {
+      if (!second.sym_len || g >= 2 * nw) return;
+      g -= nw;
+    } else if (g >= nw) {
+      return;
+    }
+    const int row = g / wg.tpr;
+    wbi = wg.bi0 + row;
+    const int64_t rb = (int64_t)wbi * nbx;
+    t = (rb + wg.bj0) / 64 + (g - row * wg.tpr);
+    if (t > (rb + wg.bj1 - 1) / 64) return;
+    wfirst = g == 0;
+  }
+  const bool b = WIN ? wsecond : (!RGB && t >= ntiles);  // wave-uniform: the second plane's tile t - ntiles
+  if constexpr (!WIN) {
+    if (b) {
+      if (!second.sym_len || t >= 2 * ntiles) return;
+      t -= ntiles;
+    } else if (t >= ntiles) {
+      return;
+    }
   }
   const uint8_t *__restrict__ sym_len = b ? second.sym_len : sym_len_a;
   const int16_t *__restrict__ sym_val = b ? second.sym_val : sym_val_a;
@@ -459,6 +549,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HIC_DEC_WPE
   uint2 *tile = s_tile[wv];
   int16_t *win = reinterpret_cast<int16_t *>(tile);
   const int64_t nsym_raw = *d_nsym, nsym = nsym_raw > 0 ? nsym_raw : 0;
+  if constexpr (WIN) {
+    if (wfirst && lane == 0) *d_status = nsym_raw < 1 ? -1 : wg.n_ac;
+    if (nsym_raw < 1) return;  // a failed encode's count: nothing is decoded or stored
+  }
   const int nvb = (int)(nblk - t * 64 < 64 ? nblk - t * 64 : 64);
   const int64_t blk = t * 64 + lane;
   // loads that depend on nothing else go out before the zero-fill: this lane's DC
@@ -489,13 +583,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HIC_DEC_WPE
   win[lane * kRowI16] = (int16_t)(pdc + wave_incl_sum_i32(d));
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_s_setprio(0);
-  if (t == ntiles - 1 && lane == 0) {
+  if (!WIN && t == ntiles - 1 && lane == 0) {
     // (a slot-layout stream is whole by construction: its EOB zero-fills the rest)
     const int64_t total = tb0 + (int64_t)P, n_ac = nblk * 63;
     const bool eob = SLOTS || (nsym > 0 && sym_len[nsym - 1] == 0 && sym_val[nsym - 1] == 0);
     *d_status = nsym_raw < 1 ? -1 : ((eob && (SLOTS || total <= n_ac)) ? n_ac : total);
   }
   if (!RGB && lane >= nvb) return;
+  if constexpr (WIN && !RGB) {
+    // the plane form needs no lane outside the window: only blocks of this wave's row
+    const int wi = (int)(blk / nbx), wj = (int)(blk - (int64_t)wi * nbx);
+    if (wi != wbi || wj < wg.bj0 || wj >= wg.bj1) return;
+  }
   int qv[64];  // raster [u][v]
   {
     const uint2 *row = tile + (lane < nvb ? lane : nvb - 1) * (kRowI16 / 4);
@@ -513,7 +612,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HIC_DEC_WPE
   if (RGB) {
     uint32_t px[16];
     idct_block_px<TABLE>(qv, px);
-    colour_block(px, bi, bj, nbx, H / 8, lane, lane < nvb, cr, cb, out, ostride);
+    if constexpr (WIN) colour_block<true>(px, bi, bj, nbx, H / 8, lane, lane < nvb, cr, cb, out, ostride, wg, wbi);
+    else colour_block(px, bi, bj, nbx, H / 8, lane, lane < nvb, cr, cb, out, ostride);
+  } else if constexpr (WIN) {
+    idct_block_store<TABLE, true>(qv, H, W, bi * 8 - wg.oy, bj * 8 - wg.ox, out, ostride);
   } else {
     idct_block_store<TABLE, FAST>(qv, H, W, bi * 8, bj * 8, out, ostride);
   }
@@ -1030,7 +1132,7 @@ struct DecLaunch {
 
 // Every check before any device call; then the grid and the kernel for (table, whole
 // blocks, RGB, stream kind).
-static int launch_rld_idct(const DecLaunch &d, void *stream) {
+static int dec_planes_ok(const DecLaunch &d) {
   for (int k = 0; k < d.nplanes; ++k) {
     const DecPlane &p = d.p[k];
     char who[16] = "";
@@ -1042,6 +1144,10 @@ static int launch_rld_idct(const DecLaunch &d, void *stream) {
     if (!aligned(p.sym_len, 16) || !aligned(p.sym_val, 16))
       return arg_error("%s%s arrays must be 16-byte aligned", who, d.slots ? "slot" : "symbol");
   }
+  return HIC_OK;
+}
+static int launch_rld_idct(const DecLaunch &d, void *stream) {
+  if (int e = dec_planes_ok(d)) return e;
   if (d.rgb) {
     // the RGB form has no ragged path: whole 8x8 blocks, 8-byte pixel stores
     if (!dims_ok(d.H, d.W) || d.H % 8 || d.W % 8) return arg_error("plane shape (H, W multiples of 8)");
@@ -1160,6 +1266,132 @@ extern "C" int hic_rle_decode_idct_rgb_slots(const uint8_t *slot_len, const int1
   d.rgb = true, d.cr = cr, d.cb = cb;
   d.slots = true, d.records_per_tile = records_per_tile;
   return launch_rld_idct(d, stream);
+}
+
+// ---- region decode: the window forms of the same kernel (DESIGN.md section 5,
+// "Region decode").  hic_window_plan is the one statement of the geometry; the entry
+// points accept only a window that equals the plan of its own aligned rectangle.
+static int window_plan(int64_t H, int64_t W, int64_t y0, int64_t x0, int64_t h, int64_t w, hic_window *o) {
+  if (!dims_ok(H, W) || H % 16 || W % 16) return arg_error("image shape (H, W multiples of 16)");
+  if (h < 1 || w < 1 || y0 < 0 || x0 < 0 || y0 > H - h || x0 > W - w) return arg_error("window outside the image");
+  auto dn = [](int64_t v, int64_t a) { return v / a * a; };
+  auto up = [](int64_t v, int64_t a) { return (v + a - 1) / a * a; };
+  o->Y0 = dn(y0, 16), o->X0 = dn(x0, 16), o->Y1 = up(y0 + h, 16), o->X1 = up(x0 + w, 16);
+  // pyrUp's one-sample halo around chroma rows [Y0/2, Y1/2), clipped to the plane and
+  // rounded out to whole 8x8 chroma blocks (H/2, W/2 are multiples of 8)
+  const int64_t hc = H / 2, wc = W / 2;
+  auto lo = [&](int64_t a) { return dn(a / 2 - 1 < 0 ? 0 : a / 2 - 1, 8); };
+  auto hi = [&](int64_t b, int64_t n) { return up(b / 2 + 1 > n ? n : b / 2 + 1, 8); };
+  o->cy0 = lo(o->Y0), o->cx0 = lo(o->X0);
+  o->ch = hi(o->Y1, hc) - o->cy0, o->cw = hi(o->X1, wc) - o->cx0;
+  return HIC_OK;
+}
+
+extern "C" int hic_window_plan(int64_t H, int64_t W, int64_t y0, int64_t x0, int64_t h, int64_t w, hic_window *out) {
+  if (!out) return arg_error("null pointer");
+  return window_plan(H, W, y0, x0, h, w, out);
+}
+
+// the most tiles one block row's columns [bj0, bj1) touch (rows [bi0, bi0 + nrows))
+static int tiles_per_row(int nbx, int bi0, int nrows, int bj0, int bj1) {
+  int m = 1;
+  for (int bi = bi0; bi < bi0 + nrows; ++bi) {
+    const int64_t rb = (int64_t)bi * nbx;
+    const int n = (int)((rb + bj1 - 1) / 64 - (rb + bj0) / 64) + 1;
+    m = n > m ? n : m;
+  }
+  return m;
+}
+
+// d.H, d.W: the IMAGE's shape (the chroma pair's planes are H/2 x W/2); cstride: the
+// RGB form's chroma pitch.  Every check before any device call.
+static int launch_rld_idct_window(const DecLaunch &d, int kind, const hic_window *win, int64_t cstride, void *stream) {
+  if (kind != HIC_STREAM_INDEXED && kind != HIC_STREAM_SLOTS) return arg_error("stream kind");
+  if (int e = dec_planes_ok(d)) return e;
+  if (!win) return arg_error("null pointer");
+  const hic_window &w = *win;
+  if (w.Y0 % 16 || w.X0 % 16 || w.Y1 % 16 || w.X1 % 16) return arg_error("the window must be 16-pixel aligned");
+  hic_window want;
+  if (int e = window_plan(d.H, d.W, w.Y0, w.X0, w.Y1 - w.Y0, w.X1 - w.X0, &want)) return e;
+  if (w.cy0 != want.cy0 || w.cx0 != want.cx0 || w.ch != want.ch || w.cw != want.cw)
+    return arg_error("the window's chroma span is not hic_window_plan's");
+  const int64_t pH = d.rgb ? d.H : d.H / 2, pW = d.rgb ? d.W : d.W / 2;
+  if (d.rgb) {
+    if (d.out_stride < 3 * (w.X1 - w.X0) || d.out_stride % 8 || !aligned(d.p[0].out, 8))
+      return arg_error("rgb stride / alignment (8 B)");
+    // colour_block loads chroma dwords
+    if (!aligned(d.cr, 4) || !aligned(d.cb, 4)) return arg_error("chroma planes must be 4-byte aligned");
+    if (cstride < w.cw || cstride % 4) return arg_error("chroma pitch (>= the span, a multiple of 4)");
+    if (w.ch * cstride >= ((int64_t)1 << 31)) return arg_error("chroma window too large");
+  } else {
+    // 8-byte row stores (and the RGB form's dword loads: 4 | 8)
+    if (d.out_stride < w.cw || d.out_stride % 8) return arg_error("chroma pitch (>= the span, a multiple of 8)");
+    for (int k = 0; k < d.nplanes; ++k)
+      if (!aligned(d.p[k].out, 8)) return arg_error("plane %d: chroma planes must be 8-byte aligned", k);
+  }
+  const int nbx = (int)(pW / 8);
+  const int64_t nblk = (int64_t)nbx * (pH / 8);
+  if (nblk * 63 >= ((int64_t)1 << 31)) return arg_error("plane too large (AC stream >= 2^31)");
+  if (d.slots) {
+    if (d.records_per_tile != 1 && d.records_per_tile != 2) return arg_error("records_per_tile must be 1 or 2");
+    if (nblk % (64 / d.records_per_tile)) return arg_error("the plane's blocks must form whole records");
+  }
+  WinGeo g{};
+  if (d.rgb) {
+    g.bi0 = (int)(w.Y0 / 8), g.nrows = (int)((w.Y1 - w.Y0) / 8), g.bj0 = (int)(w.X0 / 8), g.bj1 = (int)(w.X1 / 8);
+    g.oy = (int)w.Y0, g.ox = (int)w.X0;
+  } else {
+    g.bi0 = (int)(w.cy0 / 8), g.nrows = (int)(w.ch / 8), g.bj0 = (int)(w.cx0 / 8), g.bj1 = (int)((w.cx0 + w.cw) / 8);
+    g.oy = (int)w.cy0, g.ox = (int)w.cx0;
+  }
+  g.cy0 = (int)w.cy0, g.cx0 = (int)w.cx0, g.ch = (int)w.ch, g.cw = (int)w.cw, g.cpitch = (int)cstride;
+  g.tpr = tiles_per_row(nbx, g.bi0, g.nrows, g.bj0, g.bj1);
+  g.n_ac = (int64_t)g.nrows * (g.bj1 - g.bj0) * 63;
+  const int64_t waves = (int64_t)d.nplanes * g.nrows * g.tpr;
+  const dim3 grid((unsigned)((waves + 3) / 4)), block(256);
+  hipStream_t s = as_stream(stream);
+  const DecPlane &a = d.p[0], second = d.nplanes > 1 ? d.p[1] : DecPlane{};
+  const int rsh = d.slots && d.records_per_tile == 2 ? 1 : 0;
+#define HIC_DEC_WIN(T, R, S)                                                                                      \
+  hipLaunchKernelGGL((k_rld_idct_indexed<T, true, R, S, true>), grid, block, 0, s, a.sym_len, a.sym_val, a.d_nsym, \
+                     a.dc_diff, a.index, (int)pH, (int)pW, nbx, nblk, a.out, d.out_stride, a.d_status, d.cr, d.cb, \
+                     second, rsh, g)
+  if (d.rgb && d.slots) HIC_DEC_WIN(0, true, true);
+  else if (d.rgb) HIC_DEC_WIN(0, true, false);
+  else if (d.slots) HIC_DEC_WIN(1, false, true);
+  else HIC_DEC_WIN(1, false, false);
+#undef HIC_DEC_WIN
+  return check_launch("k_rld_idct_indexed<window>");
+}
+
+extern "C" int hic_rle_decode_idct_u8_window_pair(int kind, const uint8_t *const *h_sym_len,
+                                                  const int16_t *const *h_sym_val, const int64_t *const *h_d_nsym,
+                                                  const int32_t *const *h_dc_diff, const void *const *h_d_index,
+                                                  int records_per_tile, int64_t H, int64_t W, const hic_window *win,
+                                                  uint8_t *const *h_out, int64_t out_stride,
+                                                  int64_t *const *h_d_status, void *stream) {
+  if (!h_sym_len || !h_sym_val || !h_d_nsym || !h_dc_diff || !h_d_index || !h_out || !h_d_status)
+    return arg_error("null pointer");
+  DecLaunch d{};
+  for (int k = 0; k < 2; ++k)
+    d.p[k] = DecPlane{h_sym_len[k], h_sym_val[k], h_d_nsym[k], h_dc_diff[k],
+                      static_cast<const int64_t *>(h_d_index[k]), h_out[k], h_d_status[k]};
+  d.nplanes = 2, d.H = H, d.W = W, d.table_id = HIC_TABLE_CHROMINANCE, d.out_stride = out_stride;
+  d.slots = kind == HIC_STREAM_SLOTS, d.records_per_tile = records_per_tile;
+  return launch_rld_idct_window(d, kind, win, 0, stream);
+}
+
+extern "C" int hic_rle_decode_idct_rgb_window(int kind, const uint8_t *sym_len, const int16_t *sym_val,
+                                              const int64_t *d_nsym, const int32_t *dc_diff, const void *d_index,
+                                              int records_per_tile, int64_t H, int64_t W, const hic_window *win,
+                                              const uint8_t *cr, const uint8_t *cb, int64_t chroma_stride,
+                                              uint8_t *rgb, int64_t rgb_stride, int64_t *d_status, void *stream) {
+  DecLaunch d{};
+  d.p[0] = DecPlane{sym_len, sym_val, d_nsym, dc_diff, static_cast<const int64_t *>(d_index), rgb, d_status};
+  d.nplanes = 1, d.H = H, d.W = W, d.table_id = HIC_TABLE_LUMINANCE, d.out_stride = rgb_stride;
+  d.rgb = true, d.cr = cr, d.cb = cb;
+  d.slots = kind == HIC_STREAM_SLOTS, d.records_per_tile = records_per_tile;
+  return launch_rld_idct_window(d, kind, win, chroma_stride, stream);
 }
 
 extern "C" int hic_dct2_f64(const double *in, int64_t nblk, double *out, void *stream) {

@@ -1585,6 +1585,126 @@ __global__ __launch_bounds__(256) void k_rle_index16(const int64_t *__restrict__
   index[3 * t + 2] = t > 0 ? (int64_t)blocks[(t * 64 - 1) * 64] : 0;
 }
 
+// The same three words from a bare contiguous stream (hic_rle_stream_index_i16): no
+// blocks, no encoder workspace.  Symbol i ends at position e_i = sum_{j <= i}(len_j + 1)
+// - 1, strictly increasing in i.  The encoder books a nonzero's symbols (its fillers
+// and its value symbol) to the tile that holds the nonzero, so for tile t with first AC
+// position tb0 the words are j + 1 and e_j for j = the last symbol with a nonzero value
+// and e_j < tb0 (0 and -1 when there is none): fillers and the EOB have value 0 and
+// never count.  A carried run can span the whole channel as fillers, so j is not
+// searched backwards: per symbol tile (kDTS symbols) the last nonzero symbol is found
+// once (k_sym_lastnz), scanned to "last nonzero symbol before symbol tile k"
+// (k_lastnz_scan), and each coefficient tile looks only into the one symbol tile that
+// position tb0 falls in (k_stream_index).
+// The last symbol i of symbol tile k (first position `start`) with a nonzero value and
+// e_i < limit: its index and e_i as the workgroup's maxima (-1: none).
+__device__ __forceinline__ void tile_last_nz(const uint8_t *__restrict__ sym_len, const int16_t *__restrict__ sym_val,
+                                             int64_t nsym, int64_t k, int64_t start, int64_t limit, int64_t *s_buf,
+                                             int64_t &idx, int64_t &pos) {
+  const int64_t s0 = k * kDTS + (int64_t)threadIdx.x * kDS;
+  int len[kDS], val[kDS];
+  if (s0 + kDS <= nsym) {
+    const uint4 l = *reinterpret_cast<const uint4 *>(sym_len + s0);
+    const uint4 v0 = *reinterpret_cast<const uint4 *>(sym_val + s0), v1 = *reinterpret_cast<const uint4 *>(sym_val + s0 + 8);
+    const uint32_t lw[4] = {l.x, l.y, l.z, l.w}, vw[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+#pragma unroll
+    for (int j = 0; j < kDS; ++j) {
+      len[j] = (int)((lw[j >> 2] >> (8 * (j & 3))) & 255u);
+      val[j] = (int)((vw[j >> 1] >> (16 * (j & 1))) & 0xFFFFu);
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < kDS; ++j) {
+      const bool in = s0 + j < nsym;  // past the stream: length -1 (no positions), value 0
+      len[j] = in ? (int)sym_len[s0 + j] : -1;
+      val[j] = in ? (int)sym_val[s0 + j] : 0;
+    }
+  }
+  int64_t acc = 0;
+#pragma unroll
+  for (int j = 0; j < kDS; ++j) acc += len[j] + 1;
+  int64_t total;
+  int64_t e = start + block_excl_sum<int64_t, kTB>(acc, s_buf, total) - 1;  // e_i of the symbol before the lane's
+  int64_t li = -1, lp = -1;
+#pragma unroll
+  for (int j = 0; j < kDS; ++j) {
+    e += len[j] + 1;
+    if (val[j] != 0 && e < limit) li = s0 + j, lp = e;
+  }
+  block_excl_max<int64_t, kTB>(li, (int64_t)-1, s_buf, idx);
+  block_excl_max<int64_t, kTB>(lp, (int64_t)-1, s_buf, pos);
+}
+
+__global__ __launch_bounds__(kTB) void k_sym_lastnz(const uint8_t *__restrict__ sym_len,
+                                                    const int16_t *__restrict__ sym_val, int64_t nsym,
+                                                    const int64_t *__restrict__ tile_off, int64_t *__restrict__ lnz) {
+  __shared__ int64_t s_buf[8];
+  int64_t idx, pos;
+  tile_last_nz(sym_len, sym_val, nsym, blockIdx.x, tile_off[blockIdx.x], INT64_MAX, s_buf, idx, pos);
+  if (threadIdx.x == 0) lnz[2 * (int64_t)blockIdx.x] = idx, lnz[2 * (int64_t)blockIdx.x + 1] = pos;
+}
+
+// pre[2k], pre[2k + 1] = the maxima of lnz's two columns over tiles < k, for k in [0, n]
+// (both columns grow with the tile wherever a tile has a nonzero).  One workgroup.
+__global__ __launch_bounds__(kScanT) void k_lastnz_scan(const int64_t *__restrict__ lnz, int64_t n,
+                                                        int64_t *__restrict__ pre) {
+  __shared__ int64_t s_buf[32];
+  int64_t ri = -1, rp = -1;
+  for (int64_t c0 = 0; c0 <= n; c0 += kScanT) {
+    const int64_t k = c0 + threadIdx.x;
+    const int64_t vi = k < n ? lnz[2 * k] : -1, vp = k < n ? lnz[2 * k + 1] : -1;
+    int64_t ai, ap;
+    const int64_t ei = block_excl_max<int64_t, kScanT>(vi, (int64_t)-1, s_buf, ai);
+    const int64_t ep = block_excl_max<int64_t, kScanT>(vp, (int64_t)-1, s_buf, ap);
+    if (k <= n) pre[2 * k] = ei > ri ? ei : ri, pre[2 * k + 1] = ep > rp ? ep : rp;
+    ri = ai > ri ? ai : ri, rp = ap > rp ? ap : rp;
+  }
+}
+
+// One workgroup per 64-block coefficient tile.  tile_off: the symbol tiles' first
+// positions (exclusive scan of k_rld_tile16's sums), *tot the stream's positions;
+// dc_off: the exclusive scan of k_dc_tile's sums (kTS blocks per DC tile).
+__global__ __launch_bounds__(kTB) void k_stream_index(const uint8_t *__restrict__ sym_len,
+                                                      const int16_t *__restrict__ sym_val, int64_t nsym, int64_t nts,
+                                                      const int64_t *__restrict__ tile_off,
+                                                      const int64_t *__restrict__ tot, const int64_t *__restrict__ pre,
+                                                      const int32_t *__restrict__ dc_diff,
+                                                      const int64_t *__restrict__ dc_off, int64_t *__restrict__ index) {
+  __shared__ int64_t s_buf[8];
+  const int64_t t = blockIdx.x, tb0 = t * 64 * 63;
+  // the first symbol tile that ends past position tb0 (workgroup-uniform)
+  int64_t lo = 0, hi = nts;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    const int64_t end = mid + 1 < nts ? tile_off[mid + 1] : *tot;
+    if (end > tb0) hi = mid;
+    else lo = mid + 1;
+  }
+  int64_t idx = pre[2 * lo], pos = pre[2 * lo + 1];
+  if (lo < nts) {
+    int64_t i2, p2;
+    tile_last_nz(sym_len, sym_val, nsym, lo, tile_off[lo], tb0, s_buf, i2, p2);
+    idx = i2 > idx ? i2 : idx, pos = p2 > pos ? p2 : pos;
+  }
+  // DC of block 64t - 1: the DC tile's offset plus its differences up to that block
+  int64_t dcv = 0;
+  if (t > 0) {
+    const int64_t dt = (64 * t - 1) / kTS, b0 = dt * kTS + (int64_t)threadIdx.x * kSPT;
+    int64_t acc = 0;
+#pragma unroll
+    for (int j = 0; j < kSPT; ++j)
+      if (b0 + j < 64 * t) acc += dc_diff[b0 + j];
+    int64_t total;
+    block_excl_sum<int64_t, kTB>(acc, s_buf, total);
+    dcv = (int64_t)(int16_t)(dc_off[dt] + total);  // the encoder's word is its int16 coefficient
+  }
+  if (threadIdx.x == 0) {
+    index[3 * t] = idx + 1;
+    index[3 * t + 1] = pos;
+    index[3 * t + 2] = dcv;
+  }
+}
+
 // SLOTS: the symbols are in the slot layout (slots.h) and `index` is the close's
 // int32 record index (rsh: log2 records per 64-block tile).
 template <bool SLOTS>
@@ -1774,6 +1894,58 @@ extern "C" int hic_rle_tile_index_i16(const int16_t *blocks, int64_t nblk, int r
   hipLaunchKernelGGL(k_rle_index16, dim3((unsigned)((ntiles + 255) / 256)), dim3(256), 0, as_stream(stream), offs,
                      records_per_tile == 2 ? 1 : 0, ntiles, blocks, d_index);
   return check_launch("k_rle_index16");
+}
+
+// int64 words of hic_rle_stream_index_i16's workspace: symbol-tile offsets + the
+// scan's chunk partials, DC-tile offsets, {positions, DC total}, the last symbol, the
+// symbol tiles' last nonzeros and their scan
+static int64_t stream_index_words(int64_t nsym, int64_t nblk, int64_t off[6]) {
+  const int64_t nts = (nsym + kDTS - 1) / kDTS, ntb = (nblk + kTS - 1) / kTS;
+  int64_t w = 0;
+  off[0] = w, w += nts + 1;                                   // tsum
+  off[1] = w, w += nts / ((int64_t)kScanT * kScanK) + 2;      // scan partials
+  off[2] = w, w += ntb + 1;                                   // dsum
+  off[3] = w, w += 2;                                         // tot
+  off[4] = w, w += 4;                                         // last symbol
+  off[5] = w, w += 2 * nts + 2 * (nts + 1);                   // lnz, pre
+  return w;
+}
+
+extern "C" size_t hic_rle_stream_index_workspace_bytes(int64_t nsym, int64_t nblk) {
+  int64_t off[6];
+  return (size_t)stream_index_words(nsym > 0 ? nsym : 0, nblk > 0 ? nblk : 1, off) * 8;
+}
+
+extern "C" int hic_rle_stream_index_i16(const uint8_t *sym_len, const int16_t *sym_val, int64_t nsym,
+                                        const int32_t *dc_diff, int64_t nblk, int64_t *d_index, int64_t *d_status,
+                                        void *workspace, void *stream) {
+  if (!sym_len || !sym_val || !dc_diff || !d_index || !d_status || !workspace) return arg_error("null pointer");
+  if (nsym < 0) return arg_error("nsym");
+  if (nblk <= 0 || nblk * 63 >= ((int64_t)1 << 31)) return arg_error("nblk");
+  if ((reinterpret_cast<uintptr_t>(sym_len) | reinterpret_cast<uintptr_t>(sym_val)) % 16)
+    return arg_error("symbol arrays must be 16-byte aligned");
+  hipStream_t s = as_stream(stream);
+  int64_t off[6];
+  stream_index_words(nsym, nblk, off);
+  int64_t *w = static_cast<int64_t *>(workspace);
+  int64_t *tsum = w + off[0], *part = w + off[1], *dsum = w + off[2], *tot = w + off[3], *last = w + off[4];
+  const int64_t nts = (nsym + kDTS - 1) / kDTS, ntb = (nblk + kTS - 1) / kTS, ntiles = (nblk + kWT - 1) / kWT;
+  int64_t *lnz = w + off[5], *pre = lnz + 2 * nts;
+  if (nts > 0) {
+    hipLaunchKernelGGL(k_rld_tile16, dim3((unsigned)nts), dim3(kTB), 0, s, sym_len, nsym, tsum);
+    if (int e = check_launch("k_rld_tile16")) return e;
+  }
+  if (int e = scan_inplace(tsum, nts, tot, part, s)) return e;
+  hipLaunchKernelGGL(k_dc_tile, dim3((unsigned)ntb), dim3(kTB), 0, s, dc_diff, nblk, dsum);
+  hipLaunchKernelGGL(k_scan_inplace, dim3(1), dim3(kScanT), 0, s, dsum, ntb, tot + 1);
+  if (nts > 0) hipLaunchKernelGGL(k_sym_lastnz, dim3((unsigned)nts), dim3(kTB), 0, s, sym_len, sym_val, nsym, tsum, lnz);
+  hipLaunchKernelGGL(k_lastnz_scan, dim3(1), dim3(kScanT), 0, s, lnz, nts, pre);
+  hipLaunchKernelGGL(k_stream_index, dim3((unsigned)ntiles), dim3(kTB), 0, s, sym_len, sym_val, nsym, nts, tsum, tot,
+                     pre, dc_diff, dsum, d_index);
+  if (int e = check_launch("k_stream_index")) return e;
+  hipLaunchKernelGGL((k_last_sym<uint8_t, int16_t>), dim3(1), dim3(1), 0, s, sym_len, sym_val, nsym, last);
+  hipLaunchKernelGGL(k_rld_status, dim3(1), dim3(1), 0, s, tot, last, nblk * 63, (const int64_t *)nullptr, d_status);
+  return check_launch("k_rld_status");
 }
 
 // The one launch of k_rld_indexed16.  slots: the symbols are in the slot layout and

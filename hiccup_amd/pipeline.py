@@ -28,6 +28,7 @@ All launches are asynchronous on one stream; buffers are allocated once.
 half + compression.jpeg_decompression).  The optional ``stitch`` tensors make
 an encoder one tile-shard of a larger image (see sharding.py).
 """
+import collections
 import ctypes
 
 import numpy as np
@@ -578,3 +579,158 @@ class Decoder:
             want = self.blocks[k].shape[0] * 63
             if st[i] != want:
                 raise ValueError("channel %s: stream covers %d AC positions, expected %d" % (k, st[i], want))
+
+
+# ------------------------------------------------------------------ region decode
+class WindowPlan(collections.namedtuple("WindowPlan", "Y0 X0 Y1 X1 cy0 cx0 ch cw")):
+    """hic_window (include/hiccup_hip.h): the 16-pixel-aligned covering window
+    [Y0, Y1) x [X0, X1) of a request, and the span of the H/2 x W/2 chroma planes it
+    needs: rows [cy0, cy0 + ch) x columns [cx0, cx0 + cw)."""
+
+    def c_struct(self):
+        return _lib.Window(*self)
+
+
+def window_plan(H, W, y0, x0, h, w):
+    """The Python twin of hic_window_plan: the geometry of decoding rows [y0, y0 + h)
+    x columns [x0, x0 + w) of an H x W image (H, W multiples of 16; the window inside
+    the image, h, w >= 1).  The kernels see only the aligned window, whole luma and
+    chroma blocks; the chroma span is [Y0/2 - 1, Y1/2 + 1) -- pyrUp's one-sample halo
+    -- clipped to the plane and rounded out to whole 8x8 chroma blocks."""
+    if H < 16 or W < 16 or H % 16 or W % 16:
+        raise ValueError("region decode needs H, W multiples of 16")
+    if h < 1 or w < 1 or y0 < 0 or x0 < 0 or y0 + h > H or x0 + w > W:
+        raise ValueError("window (%d, %d, %d, %d) outside the %d x %d image" % (y0, x0, h, w, H, W))
+    Y0, X0, Y1, X1 = y0 // 16 * 16, x0 // 16 * 16, -(-(y0 + h) // 16) * 16, -(-(x0 + w) // 16) * 16
+
+    def span(a, b, n):
+        lo = max(0, a // 2 - 1) // 8 * 8
+        return lo, -(-min(n, b // 2 + 1) // 8) * 8 - lo
+
+    (cy0, ch), (cx0, cw) = span(Y0, Y1, H // 2), span(X0, X1, W // 2)
+    return WindowPlan(Y0, X0, Y1, X1, cy0, cx0, ch, cw)
+
+
+def window_tiles(plan, W, chroma=False):
+    """The (block row, 64-block tile) pairs a window launch decodes, in wave order:
+    per block row bi of the launch's blocks and its columns [bj0, bj1), the tiles
+    floor((bi nbx + bj0) / 64) .. floor((bi nbx + bj1 - 1) / 64) of the plane's raster
+    blocks (nbx blocks per row).  A tile that wraps two block rows appears once per
+    row; each appearance stores only its own row's blocks."""
+    if chroma:
+        nbx, bi0, bi1, bj0, bj1 = W // 16, plan.cy0 // 8, (plan.cy0 + plan.ch) // 8, plan.cx0 // 8, (plan.cx0 + plan.cw) // 8
+    else:
+        nbx, bi0, bi1, bj0, bj1 = W // 8, plan.Y0 // 8, plan.Y1 // 8, plan.X0 // 8, plan.X1 // 8
+    return [(bi, t) for bi in range(bi0, bi1)
+            for t in range((bi * nbx + bj0) // 64, (bi * nbx + bj1 - 1) // 64 + 1)]
+
+
+def region_capacity(H, W, max_h, max_w):
+    """((rows, columns) of the largest aligned window, (rows, columns) of the largest
+    chroma span) any request (h, w) <= (max_h, max_w) of an H x W image can plan: an
+    unaligned origin adds up to 15 pixels before rounding up to 16; the chroma span is
+    half the window plus one halo block of 8 on each side."""
+    wh, ww = min(H, -(-(max_h + 15) // 16) * 16), min(W, -(-(max_w + 15) // 16) * 16)
+    return (wh, ww), (min(H // 2, wh // 2 + 16), min(W // 2, ww // 2 + 16))
+
+
+class RegionDecoder:
+    """Decoder.decode(index=...)[y0:y0+h, x0:x0+w] without the rest of the image: only
+    the tiles holding the window's blocks are decoded (the window forms of the fused
+    tile decoders), into buffers sized for the largest window a request of at most
+    max_h x max_w can need (region_capacity): RGB plus the two chroma planes."""
+
+    def __init__(self, H, W, max_h, max_w):
+        device.require_gpu()
+        if H % 16 or W % 16 or H < 16 or W < 16:
+            raise ValueError("region decode needs H, W multiples of 16")
+        if not (1 <= max_h <= H and 1 <= max_w <= W):
+            raise ValueError("max_h, max_w must lie in the image")
+        self.H, self.W, self.max_h, self.max_w = H, W, max_h, max_w
+        (wh, ww), (ch, cw) = region_capacity(H, W, max_h, max_w)
+        self.rgb = device.empty((wh * ww * 3,), torch.uint8)
+        self.cr = device.empty((ch * cw,), torch.uint8)
+        self.cb = device.empty((ch * cw,), torch.uint8)
+        self.status = device.zeros((3,), torch.int64)
+        self.plan = None
+
+    def decode(self, y0, x0, h, w, sym_len, sym_val, counts, dc, index, stream=None):
+        """The stream arguments as Decoder.decode(index=...): an Encoder(index=True)'s
+        (or stream_index's) tile index with the contiguous symbols, or a SlotIndex;
+        counts the device count tensor (3,).  Returns a device view (h, w, 3) of the
+        window buffer, valid until the next decode; no host syncs."""
+        if h > self.max_h or w > self.max_w:
+            raise ValueError("window %d x %d exceeds this decoder's %d x %d" % (h, w, self.max_h, self.max_w))
+        plan = window_plan(self.H, self.W, y0, x0, h, w)
+        s = device.stream_ptr(stream)
+        slots = isinstance(index, SlotIndex)
+        kind = _lib.STREAM_SLOTS if slots else _lib.STREAM_INDEXED
+        if slots:
+            sym_len, sym_val = index.slot_len, index.slot_val
+
+        def src(i, k):
+            return (sym_len[k].data_ptr(), sym_val[k].data_ptr(), counts.data_ptr() + 8 * i, dc[k].data_ptr(),
+                    index[k].data_ptr())
+
+        two = lambda a, b: (ctypes.c_void_p * 2)(a, b)  # noqa: E731
+        st = [self.status.data_ptr() + 8 * i for i in range(3)]
+        win = plan.c_struct()
+        # the windows are packed: pitch = the window's own width
+        _lib.call("hic_rle_decode_idct_u8_window_pair", kind, *map(two, src(1, "cr"), src(2, "cb")),
+                  index.rpt["cr"] if slots else 0, self.H, self.W, ctypes.byref(win),
+                  two(self.cr.data_ptr(), self.cb.data_ptr()), plan.cw, two(st[1], st[2]), s)
+        Ww = plan.X1 - plan.X0
+        _lib.call("hic_rle_decode_idct_rgb_window", kind, *src(0, "lum"), index.rpt["lum"] if slots else 0, self.H,
+                  self.W, ctypes.byref(win), self.cr.data_ptr(), self.cb.data_ptr(), plan.cw, self.rgb.data_ptr(),
+                  3 * Ww, st[0], s)
+        self.plan = plan
+        return self.window()[y0 - plan.Y0:y0 - plan.Y0 + h, x0 - plan.X0:x0 - plan.X0 + w]
+
+    def window(self):
+        """The last decode's aligned window, a (Y1 - Y0, X1 - X0, 3) view."""
+        p = self.plan
+        n = (p.Y1 - p.Y0) * (p.X1 - p.X0) * 3
+        return self.rgb[:n].view(p.Y1 - p.Y0, p.X1 - p.X0, 3)
+
+    def chroma(self):
+        """The last decode's chroma span: (cr, cb) views of shape (ch, cw)."""
+        p = self.plan
+        return tuple(b[:p.ch * p.cw].view(p.ch, p.cw) for b in (self.cr, self.cb))
+
+    def expected_status(self):
+        """What a good decode leaves in self.status: 63 per block of each launch's window."""
+        p = self.plan
+        c = (p.ch // 8) * (p.cw // 8) * 63
+        return [((p.Y1 - p.Y0) // 8) * ((p.X1 - p.X0) // 8) * 63, c, c]
+
+    def check_status(self):
+        """Raise if a channel's symbol count was a failed encode's (status -1; syncs).
+        A window does not see the whole stream: its completeness is stream_index's
+        status, or the encoder's."""
+        st = self.status.cpu().tolist()
+        if st != self.expected_status():
+            raise ValueError("region decode status %r, expected %r" % (st, self.expected_status()))
+
+
+def stream_index(sym_len, sym_val, counts, dc, H, W, stream=None):
+    """The tile index of bare contiguous streams (hic_rle_stream_index_i16): per channel
+    the three int64 words per 64-block tile an Encoder(index=True) writes, built from
+    the symbols and DC differences alone -- a Huffman-decoded .hic can then take
+    Decoder.decode(index=...) and RegionDecoder.  counts: host ints per channel.
+    Returns ({channel: index tensor}, status (3,) int64 on the device: per channel
+    what the un-indexed decode would report, nblk * 63 for a whole stream)."""
+    lib = _lib.load()
+    s = device.stream_ptr(stream)
+    if isinstance(counts, torch.Tensor):
+        counts = counts.cpu().tolist()
+    status = device.zeros((3,), torch.int64)
+    index = {}
+    with device.on_stream(stream):
+        for i, k in enumerate(CHANNELS):
+            n = _nblk(*((H, W) if k == "lum" else (H // 2, W // 2)))
+            nsym = int(counts[i])
+            index[k] = device.empty((3 * -(-n // 64),), torch.int64)
+            ws = device.workspace(lib.hic_rle_stream_index_workspace_bytes(nsym, n))
+            _lib.call("hic_rle_stream_index_i16", device.ptr(sym_len[k]), device.ptr(sym_val[k]), nsym,
+                      device.ptr(dc[k]), n, device.ptr(index[k]), device.ptr(status[i:i + 1]), device.ptr(ws), s)
+    return index, status

@@ -519,6 +519,61 @@ int hic_rle_decode_idct_rgb_indexed(const uint8_t *sym_len, const int16_t *sym_v
                                     const int32_t *dc_diff, const int64_t *d_index, int64_t H, int64_t W,
                                     const uint8_t *cr, const uint8_t *cb, uint8_t *rgb, int64_t rgb_stride,
                                     int64_t *d_status, void *stream);
+/* ---- region decode: any window of an image from its streams (no reference
+ * counterpart: the result is the crop of the whole decode).
+ * hic_rle_stream_index_i16: the tile index of a bare contiguous stream -- no
+ * blocks, no encoder workspace -- in hic_rle_tile_index_i16's words (equal to the
+ * encoder's own index on a stream this library's encoder wrote), so a Huffman-
+ * decoded stream can take the indexed decoders.  *d_status receives what
+ * hic_rle_decode_i16 would report (the decoded AC length, EOB zero-fill included).
+ * workspace >= hic_rle_stream_index_workspace_bytes(nsym, nblk); sym_len 16-byte
+ * aligned; nblk * 63 < 2^31. */
+size_t hic_rle_stream_index_workspace_bytes(int64_t nsym, int64_t nblk);
+int hic_rle_stream_index_i16(const uint8_t *sym_len, const int16_t *sym_val, int64_t nsym,
+                             const int32_t *dc_diff, int64_t nblk, int64_t *d_index, int64_t *d_status,
+                             void *workspace, void *stream);
+/* The geometry of a window decode of an H x W image (H, W multiples of 16) for the
+ * request rows [y0, y0 + h) x columns [x0, x0 + w) (h, w >= 1, inside the image):
+ *  [Y0, Y1) x [X0, X1): the 16-pixel-aligned covering window, whole luma and chroma
+ *    blocks; the kernels see only it and the caller views
+ *    [y0 - Y0 : y0 - Y0 + h, x0 - X0 : x0 - X0 + w] of the window's pixels;
+ *  chroma rows [cy0, cy0 + ch) x columns [cx0, cx0 + cw) of the H/2 x W/2 planes:
+ *    [Y0/2 - 1, Y1/2 + 1) (pyrUp's one-sample halo), clipped to the plane and
+ *    rounded out to whole 8x8 chroma blocks. */
+typedef struct hic_window {
+  int64_t Y0, X0, Y1, X1;
+  int64_t cy0, cx0, ch, cw;
+} hic_window;
+int hic_window_plan(int64_t H, int64_t W, int64_t y0, int64_t x0, int64_t h, int64_t w, hic_window *out);
+#define HIC_STREAM_INDEXED 0 /* contiguous symbols + int64 tile index (hic_rle_tile_index_i16's words) */
+#define HIC_STREAM_SLOTS 1   /* the slot layout + the close's int32 record index */
+/* The window forms of hic_rle_decode_idct_u8_{indexed,slots}_pair and
+ * hic_rle_decode_idct_rgb_{indexed,slots}.  kind: HIC_STREAM_*; the stream arguments
+ * as those entry points' (records_per_tile is read for HIC_STREAM_SLOTS only); H, W:
+ * the IMAGE's shape; win: a hic_window_plan result with y0 = Y0, ... (anything else
+ * is refused).  Only the tiles holding the window's blocks are decoded, and nothing
+ * outside the window's buffers is written.
+ *  _u8_window_pair: Cr and Cb (chrominance table, planes H/2 x W/2) into two ch x cw
+ *    buffers (h_out, row pitch out_stride >= cw, a multiple of 8, 8-byte aligned):
+ *    sample (r, c) of a buffer is chroma sample (cy0 + r, cx0 + c).
+ *  _rgb_window: the luminance plane straight to RGB, (Y1 - Y0) x (X1 - X0) x 3 at
+ *    rgb (row pitch rgb_stride >= 3 (X1 - X0), a multiple of 8, 8-byte aligned),
+ *    reading cr / cb as _u8_window_pair left them (row pitch chroma_stride, a
+ *    multiple of 4, 4-byte aligned).  The bytes equal the same rectangle of
+ *    hic_rle_decode_idct_rgb_*'s output.
+ * *d_status: -1 when *d_nsym < 1 (then nothing is written), else 63 per block of the
+ * launch's window (the chroma span's blocks / the aligned window's luma blocks): a
+ * window does not see the whole stream, so its completeness is not reported here. */
+int hic_rle_decode_idct_u8_window_pair(int kind, const uint8_t *const *h_sym_len, const int16_t *const *h_sym_val,
+                                       const int64_t *const *h_d_nsym, const int32_t *const *h_dc_diff,
+                                       const void *const *h_d_index, int records_per_tile, int64_t H, int64_t W,
+                                       const hic_window *win, uint8_t *const *h_out, int64_t out_stride,
+                                       int64_t *const *h_d_status, void *stream);
+int hic_rle_decode_idct_rgb_window(int kind, const uint8_t *sym_len, const int16_t *sym_val, const int64_t *d_nsym,
+                                   const int32_t *dc_diff, const void *d_index, int records_per_tile, int64_t H,
+                                   int64_t W, const hic_window *win, const uint8_t *cr, const uint8_t *cb,
+                                   int64_t chroma_stride, uint8_t *rgb, int64_t rgb_stride, int64_t *d_status,
+                                   void *stream);
 /* One tile shard's slice of the channel stream (the sharded decode of
  * codec.jpeg_decode, codec.py:397-425): d_stitch is the shard's device record from
  * hic_rle_stitch {carry zeros, closes the stream, has previous DC, previous DC}.
