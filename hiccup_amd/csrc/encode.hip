@@ -191,8 +191,9 @@ __device__ __forceinline__ uint32_t pk_taps5(uint32_t a, uint32_t b, uint32_t c,
 //   the high / low bytes of the 4x coefficients: two v_dot4_u32_u8, the second
 //   accumulating the first >> 8, leave y = descale14(4899 r + ...) in byte 1 (Yh);
 //   Cr = sat8(descale14((r - y) 11682 + 2^21)) is byte 2 of
-//   clamp((r - y) 46728 + 4 (2^21 + 2^13), 0, 2^24 - 1), likewise Cb, and one
-//   v_perm packs Cr | Cb << 16 (c).
+//   clamp((r - y) 46728 + 4 (2^21 + 2^13), 0, 2^24 - 1); Cb likewise byte 2 of
+//   (b - y) 36964 + 4 (2^21 + 2^13), which needs no clamp (it stays inside 24 bits
+//   on every input), and one v_perm packs Cr | Cb << 16 (c).
 // Pixel k's bytes start at 3k: pixels 0, 4 (byte 0 of a dword) and 3, 7 (byte 1)
 // are read in place, pixels 1, 2, 5, 6 through v_alignbyte.
 constexpr uint32_t kYLo = 140u | 68u << 8 | 48u << 16, kYHi = 76u | 150u << 8 | 29u << 16;
@@ -223,8 +224,10 @@ __device__ __forceinline__ void ycc8(const uint32_t (&wd)[6], const YccK &K, uin
     const int r = (int)((x[k] >> sh) & 255u), b = (int)((x[k] >> (sh + 16)) & 255u);
     // opaque addend: a literal one is split off into a v_add after the clamp
     int vr = (r - y) * kCr4 + (int)K.cc4, vb = (b - y) * kCb4 + (int)K.cc4;
+    // Cr saturates at r - y = 179 (r = 255, g = 0, b <= 2).  Cb never does: b - y lies
+    // in [-226, 226] over all 2^24 inputs, vb in [67512, 16775240], inside 24 bits
+    // (tools/check/colour_dot4.py asserts the range)
     vr = vr < 0 ? 0 : (vr > 0xFFFFFF ? 0xFFFFFF : vr);
-    vb = vb < 0 ? 0 : (vb > 0xFFFFFF ? 0xFFFFFF : vb);
     c[k] = __builtin_amdgcn_perm((uint32_t)vb, (uint32_t)vr, 0x07060302u);
   }
 }

@@ -111,6 +111,24 @@ __device__ __forceinline__ uint32_t pk_min_u16(uint32_t a, uint32_t b) {
 }
 // Nonzero mask of a zig-zag int16 block held as 32 packed dwords: bit s set iff
 // slot s != 0.  v_pk_min_u16(w, 1) turns each half into its 0/1 flag.
+// The two halves of that mask before their interleave: bit k of ev set iff slot 2k
+// != 0, bit k of od iff slot 2k + 1 != 0.
+__device__ __forceinline__ void nz_masks16_eo(const uint32_t (&w)[32], uint32_t &ev, uint32_t &od) {
+  uint32_t acc[2];  // [half]: flags of even (low 16 bits) / odd (high) slots
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    acc[h] = 0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+      acc[h] |= pk_min_u16(w[16 * h + k], 0x00010001u) << k;
+    }
+  }
+  ev = (acc[0] & 0xFFFFu) | (acc[1] << 16);
+  od = (acc[0] >> 16) | (acc[1] & 0xFFFF0000u);
+}
+__device__ __forceinline__ uint64_t zip_eo(uint32_t ev, uint32_t od) {
+  return (uint64_t)zip16(ev, od) | ((uint64_t)zip16(ev >> 16, od >> 16) << 32);
+}
 __device__ __forceinline__ uint64_t nz_mask16(const uint32_t (&w)[32]) {
   uint32_t lo[2] = {0, 0}, hi[2] = {0, 0};  // [half]: flags of even / odd slots
 #pragma unroll
@@ -160,6 +178,34 @@ __device__ __forceinline__ void summarize_ac(uint64_t ac, int M, int &first, int
       nsym += div_m<MF>(j - pl - 1, M);
       pl = j;
     }
+  }
+}
+
+// summarize_ac<15> from the even / odd slot masks of nz_masks16_eo, without their
+// interleave: first, last and the count come from the two masks directly.  A run of
+// >= 15 zero slots between the first and the last nonzero holds >= 7 consecutive even
+// and >= 7 consecutive odd slots, so only a block with a run of 7 zeros in both masks
+// (over the slot pairs first / 2 .. last / 2: a superset of the span) is interleaved
+// and takes summarize_ac's exact walk.
+__device__ __forceinline__ void summarize_eo15(uint32_t ev, uint32_t od, int &first, int &last, int &nsym) {
+  ev &= ~1u;  // slot 0 is the DC
+  if ((ev | od) == 0) {
+    first = last = -1;
+    nsym = 0;
+    return;
+  }
+  const int fs = min(ev ? 2 * __builtin_ctz(ev) : 64, od ? 2 * __builtin_ctz(od) + 1 : 64);
+  const int ls = max(ev ? 62 - 2 * __builtin_clz(ev) : 0, od ? 63 - 2 * __builtin_clz(od) : 0);
+  first = fs - 1;  // AC j is slot j + 1
+  last = ls - 1;
+  nsym = __builtin_popcount(ev) + __builtin_popcount(od) - 1;
+  const uint32_t span = ((2u << (ls >> 1)) - 1u) & ~((1u << (fs >> 1)) - 1u);
+  const uint32_t ze = ~ev & span, zo = ~od & span;
+  const uint32_t ze2 = ze & (ze >> 1), zo2 = zo & (zo >> 1);
+  const uint32_t ze7 = ze2 & (ze2 >> 2) & (ze2 >> 4) & (ze >> 6), zo7 = zo2 & (zo2 >> 2) & (zo2 >> 4) & (zo >> 6);
+  if (ze7 != 0 && zo7 != 0) {
+    int f2, l2;
+    summarize_ac<15>(zip_eo(ev, od) >> 1, 15, f2, l2, nsym);
   }
 }
 

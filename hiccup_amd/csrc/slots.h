@@ -90,6 +90,44 @@ __device__ __forceinline__ void slot_symbols_general(const uint32_t (&zw)[32], i
   }
 }
 
+// The two rare emissions of slot_pass, out of line and one copy each (the general
+// loop is 63 unrolled steps; inlined into every pass, twice, it was two thirds of
+// the slot kernel's code).  The block goes by value, so it stays in VGPRs.
+//   wide   : a lane's symbols straight to its record's slot in HBM;
+//   packed : a lane's symbols as packed words into the stage (sb: the LDS byte
+//            address of the record's first word).
+__device__ __forceinline__ void slot_unpack8(uint32_t (&zw)[32], const uint4 (&z)[8]) {
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    zw[4 * k] = z[k].x; zw[4 * k + 1] = z[k].y; zw[4 * k + 2] = z[k].z; zw[4 * k + 3] = z[k].w;
+  }
+}
+__device__ __attribute__((noinline)) void slot_block_wide(uint4 z0, uint4 z1, uint4 z2, uint4 z3, uint4 z4, uint4 z5,
+                                                          uint4 z6, uint4 z7, int first, int o, int nf0, int rem,
+                                                          uint8_t *gl, int16_t *gv) {
+  const uint4 z[8] = {z0, z1, z2, z3, z4, z5, z6, z7};
+  uint32_t zw[32];
+  slot_unpack8(zw, z);
+  slot_symbols_general(zw, first, o, nf0, rem, [&](int i, int len, int v) {
+    gl[i] = (uint8_t)len;
+    gv[i] = (int16_t)v;
+  });
+}
+__device__ __attribute__((noinline)) void slot_block_packed(uint4 z0, uint4 z1, uint4 z2, uint4 z3, uint4 z4, uint4 z5,
+                                                            uint4 z6, uint4 z7, int first, int o, int nf0, int rem,
+                                                            uint32_t sb) {
+  const uint4 z[8] = {z0, z1, z2, z3, z4, z5, z6, z7};
+  uint32_t zw[32];
+  slot_unpack8(zw, z);
+  slot_symbols_general(zw, first, o, nf0, rem, [&](int i, int len, int v) {
+    *(lds_u16 *)(uintptr_t)(sb + 2u * (uint32_t)i) = (uint16_t)(((uint32_t)v << 4) | (uint32_t)len);
+  });
+}
+#define HIC_SLOT_Z4(zw, k) make_uint4(zw[4 * (k)], zw[4 * (k) + 1], zw[4 * (k) + 2], zw[4 * (k) + 3])
+#define HIC_SLOT_Z32(zw)                                                                                     \
+  HIC_SLOT_Z4(zw, 0), HIC_SLOT_Z4(zw, 1), HIC_SLOT_Z4(zw, 2), HIC_SLOT_Z4(zw, 3), HIC_SLOT_Z4(zw, 4), \
+      HIC_SLOT_Z4(zw, 5), HIC_SLOT_Z4(zw, 6), HIC_SLOT_Z4(zw, 7)
+
 // One pass's emission (see the file comment).  zw: this lane's block; st2: the
 // wave's stage, still holding every block (this lane's in row `lane`).  SEG: lanes
 // 0-31 hold record A's 32 blocks and 32-63 record B's (the chroma pass, Cr and
@@ -107,10 +145,12 @@ __device__ __forceinline__ void slot_pass(const uint32_t (&zw)[32], uint2 *st2, 
   const bool live = !(OPT_B && hi && b_absent);  // (constant true without OPT_B)
   const SlotRec &R = hi ? B : A;
   // ---- 1. the block's summary
-  const uint64_t ac = nz_mask16(zw) >> 1;  // bit j = AC j
+  uint32_t ev, od;  // nonzero flags of the even / odd zig-zag slots
+  nz_masks16_eo(zw, ev, od);
   int first, last, nsym;
-  summarize_ac<kSlotM>(ac, kSlotM, first, last, nsym);
-  const bool dense = nsym == __builtin_popcountll(ac) - 1;  // no run >= 15 inside the block
+  summarize_eo15(ev, od, first, last, nsym);
+  // no run >= 15 inside the block
+  const bool dense = nsym == __builtin_popcount(ev & ~1u) + __builtin_popcount(od) - 1;
   // the first nonzero's value, from the stage before it is overwritten
   const int vfirst = first >= 0 ? reinterpret_cast<const int16_t *>(st2 + lane * kStageU2)[1 + first] : 0;
   // DC differences inside the record; its first block keeps its raw DC (the close
@@ -148,15 +188,8 @@ __device__ __forceinline__ void slot_pass(const uint32_t (&zw)[32], uint2 *st2, 
     wide = __builtin_amdgcn_ballot_w64(v3 > 2047 || v3 < -2048) != 0;
   }
   __builtin_amdgcn_wave_barrier();  // every block is in registers: the stage is free
-  if (wide) {  // rare: each lane writes its symbols straight to the slot
-    if (first >= 0) {
-      uint8_t *gl = R.len;
-      int16_t *gv = R.val;
-      slot_symbols_general(zw, first, o, nf0, rem, [&](int i, int len, int v) {
-        gl[i] = (uint8_t)len;
-        gv[i] = (int16_t)v;
-      });
-    }
+  if (__builtin_expect(wide, 0)) {  // rare: each lane writes its symbols straight to the slot
+    if (first >= 0) slot_block_wide(HIC_SLOT_Z32(zw), first, o, nf0, rem, R.len, R.val);
     __builtin_amdgcn_wave_barrier();
     return;
   }
@@ -193,11 +226,8 @@ __device__ __forceinline__ void slot_pass(const uint32_t (&zw)[32], uint2 *st2, 
     for (int k = 0; k < nf0; ++k) sb[o + k] = (uint16_t)(kSlotM - 1);
     sb[o + nf0] = (uint16_t)(((uint32_t)vfirst << 4) | (uint32_t)rem);
   }
-  if (__builtin_amdgcn_ballot_w64(!dense && first >= 0)) {
-    if (!dense && first >= 0)
-      slot_symbols_general(zw, first, o, nf0, rem, [&](int i, int len, int v) {
-        sb[i] = (uint16_t)(((uint32_t)v << 4) | (uint32_t)len);
-      });
+  if (__builtin_expect(__builtin_amdgcn_ballot_w64(!dense && first >= 0) != 0, 0)) {
+    if (!dense && first >= 0) slot_block_packed(HIC_SLOT_Z32(zw), first, o, nf0, rem, lds_addr(sb));
   }
   __builtin_amdgcn_wave_barrier();
   // ---- 4. copy out, every store instruction 1 KiB contiguous: lengths 16 symbols
