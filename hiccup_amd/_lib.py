@@ -137,6 +137,10 @@ SIGNATURES = {
     "hic_rle_slots_workspace_bytes": (_sz, [_i64, _int]),
     "hic_encode420_slots_u8": (_int, [_vp, _i64, _i64, _vp, _int, _vp, _vp, _vp]),
     "hic_rle_slots_close": (_int, [_int, _vp, _int, _vp]),
+    "hic_slots_batch_table_bytes": (_sz, [_int]),
+    "hic_slots_batch_table": (_int, [_int, _i64, _i64, _vp, _vp, _sz]),
+    "hic_encode420_slots_batch_u8": (_int, [_vp, _i64, _vp, _vp, _int, _vp, _vp, _vp]),
+    "hic_rle_slots_close_batch": (_int, [_vp, _vp, _int, _vp]),
     "hic_probe_encode420_slots": (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp]),
     "hic_rle_slots_compact": (_int, [_int, _vp, _int, _vp]),
     "hic_slot_key_range": (_int, [_int, _vp, _int, _vp, _vp]),

@@ -466,6 +466,50 @@ def _encode(rgb_image):
     return enc.hic_image(from_slots=True)
 
 
+def encode_batch(images):
+    """n same-shape H x W x 3 uint8 images -- a sequence of numpy arrays or device
+    tensors, or one stacked (n, H, W, 3) array or tensor -> [HicImage], each byte for
+    byte encode(image).  Host input goes up in one copy; the n images are encoded by
+    one fused launch and closed by one scan launch (pipeline.BatchEncoder), then the
+    Huffman stage runs per image (its nine trees per image stay on the host).  A shape
+    the batch refuses, or mixed shapes, goes through encode per image."""
+    with _gc_paused():
+        return _encode_batch(images)
+
+
+def _encode_batch(images):
+    from . import pipeline
+    stacked = isinstance(images, (np.ndarray, torch.Tensor))
+    if stacked and images.ndim != 4:
+        raise ValueError("encode_batch expects n H x W x 3 uint8 images")
+    items = images if stacked else list(images)
+    n = len(items)
+    if n == 0:
+        return []
+    if not stacked:
+        items = [x if isinstance(x, torch.Tensor) else np.asarray(x) for x in items]
+    first = items[0]
+    on_device = isinstance(first, torch.Tensor)
+    same = stacked or all(isinstance(x, torch.Tensor) == on_device and x.shape == first.shape and x.dtype == first.dtype
+                          for x in items)
+    ok = (same and first.ndim == 3 and first.shape[2] == 3 and first.dtype == (torch.uint8 if on_device else np.uint8)
+          and settings.JPEG_BLOCK_SIZE == 8
+          and pipeline.batch_slots_eligible(n, int(first.shape[0]), int(first.shape[1])))
+    if not ok:
+        return [_encode(x) for x in items]
+    H, W = int(first.shape[0]), int(first.shape[1])
+    if on_device:
+        x = images if stacked else torch.stack(list(items))
+        if tuple(x.stride()[1:]) != (3 * W, 3, 1) or (n > 1 and x.stride(0) % 8):
+            x = x.contiguous()
+        x = x.cuda() if not x.is_cuda else x
+    else:
+        x = device.to_device(np.ascontiguousarray(images) if stacked else np.stack(items))
+    batch = pipeline.BatchEncoder(n, H, W)
+    batch.encode(x)
+    return batch.hic_images(from_slots=True)
+
+
 def decode(hic_image):
     """HicImage -> RGB uint8 numpy array, == compression.jpeg_decompression(
     jpeg_decode(hic_image)), without the float64 planes' round trip through the

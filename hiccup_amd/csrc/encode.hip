@@ -54,6 +54,7 @@
 #include "dct_core.h"
 #include "rle_core.h"
 #include "slots.h"
+#include "slots_batch.h"
 
 namespace hic {
 namespace {
@@ -745,6 +746,57 @@ __global__ __launch_bounds__(64 * HIC_ENC_WPB) __attribute__((amdgpu_waves_per_e
   encode_unit<TMF, false>(B.e[j], g - B.unit0[j], lane, s_stage + wv * 64 * kStageU2, s_chroma_all[wv]);
 }
 
+// N whole images of one shape in the slot layout in ONE launch
+// (hic_encode420_slots_batch_u8, slots_batch.h): the grid is n x the one-image grid,
+// flattened; logical workgroup bx is workgroup bx % wpi of image bx / wpi, and
+// xcd_block runs on the flattened index, so the consecutive workgroups of an image
+// share an XCD's L2 as in the one-image launch.  The image's 15 pointers come from
+// its table entry by wave-uniform (scalar) loads of constant memory -- the table is
+// written only by the host -- and its RGB base in 64 bits: E.rgb feeds EncColour::
+// init's readfirstlane'd buffer resource, so the 32-bit offsets cover one image.
+struct Enc420Table {
+  const uint8_t *rgb;
+  int64_t stride;  // bytes between two images' first pixels
+  const SlotBatchEntry *tab;
+  int H, W, nstrips, nunits;
+  int wpi;  // workgroups per image
+  int xcd, alt;
+};
+
+template <bool BAND>
+__global__ __launch_bounds__(64 * HIC_ENC_WPB) __attribute__((amdgpu_waves_per_eu(3))) void k_encode420_slots_batch(
+    Enc420Table T) {
+  __shared__ __attribute__((aligned(16))) uint2 s_stage[HIC_ENC_WPB * 64 * kStageU2];
+  __shared__ uint32_t s_chroma_all[HIC_ENC_WPB][2 * 8 * 64];
+  const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int bf = __builtin_amdgcn_readfirstlane(T.xcd ? xcd_block((int)blockIdx.x, (int)gridDim.x) : (int)blockIdx.x);
+  const int img = __builtin_amdgcn_readfirstlane(bf / T.wpi), bx = __builtin_amdgcn_readfirstlane(bf - img * T.wpi);
+  typedef const __attribute__((address_space(4))) SlotBatchEntry *EntryP;
+  const EntryP ent = (EntryP)(reinterpret_cast<uintptr_t>(T.tab) + (uintptr_t)img * sizeof(SlotBatchEntry));
+  Enc420 E{};
+  E.rgb = T.rgb + (int64_t)img * T.stride;
+  E.in_rows = E.H = E.out_rows = T.H;
+  E.W = T.W;
+  E.M = kSlotM;
+  E.nstrips = T.nstrips;
+  E.nunits = T.nunits;
+  E.wlast = 512;
+  E.xcd = T.xcd;
+  E.alt = T.alt;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    E.slen[k] = ent->c[k].slot_len;
+    E.sval[k] = ent->c[k].slot_val;
+    E.dc[k] = ent->c[k].dc_diff;
+    E.rec[k] = ent->c[k].ws;
+    E.rdc[k] = ent->c[k].rdc;
+  }
+  const int g = enc_unit_of<BAND>(E, bx, wv);
+  if constexpr (!BAND)
+    if (g >= E.nunits) return;  // wave-uniform
+  encode_unit<kSlotM, true, BAND>(E, g, lane, s_stage + wv * 64 * kStageU2, s_chroma_all[wv], wv);
+}
+
 // Memory-only probe of k_encode420's byte pattern (bench.py's in-run floor for the
 // fused kernel): the same grid, unit order and 19 row loads per unit, the LDS stage
 // and the three passes' 1 KiB nontemporal stores plus their records, no colour
@@ -1053,6 +1105,45 @@ extern "C" int hic_encode420_slots_u8(const uint8_t *rgb, int64_t H, int64_t W, 
   };
   band ? launch(k_encode420<kSlotM, true, true>) : launch(k_encode420<kSlotM, true>);
   return check_launch("k_encode420<slots>");
+}
+
+extern "C" int hic_encode420_slots_batch_u8(const uint8_t *rgb, int64_t image_stride, const void *h_table,
+                                            const void *d_table, int max_len, void *stream, void *ev_start,
+                                            void *ev_stop) {
+  if (!rgb || !h_table || !d_table) return arg_error("null pointer");
+  if (max_len != kSlotM) return arg_error("the slot layout needs max_len 15");
+  if (reinterpret_cast<uintptr_t>(d_table) % 16) return arg_error("d_table must be 16-byte aligned");
+  SlotBatchHeader h;
+  memcpy(&h, h_table, sizeof h);
+  if (const char *e = slot_batch_header_error(h)) return arg_error(e);
+  if (reinterpret_cast<uintptr_t>(rgb) % 8) return arg_error("rgb must be 8-byte aligned");
+  if (image_stride < h.H * h.W * 3 || image_stride % 8)
+    return arg_error("image_stride %lld: at least H * W * 3 = %lld and a multiple of 8", (long long)image_stride,
+                     (long long)(h.H * h.W * 3));
+  Enc420 O{};
+  const bool band = enc_order(O);
+  Enc420Table T{};
+  T.rgb = rgb;
+  T.stride = image_stride;
+  T.tab = reinterpret_cast<const SlotBatchEntry *>(static_cast<const char *>(d_table) + sizeof h);
+  T.H = (int)h.H;
+  T.W = (int)h.W;
+  T.nstrips = h.nstrips;
+  T.nunits = h.nunits;
+  T.wpi = band ? h.wg_band : h.wg_flat;
+  T.xcd = O.xcd;
+  T.alt = O.alt;
+  const dim3 grid((unsigned)(h.n * T.wpi)), block(64 * HIC_ENC_WPB);
+  const hipStream_t s = as_stream(stream);
+  const hipEvent_t e0 = static_cast<hipEvent_t>(ev_start), e1 = static_cast<hipEvent_t>(ev_stop);
+  auto launch = [&](auto kern) {
+    if (e0 || e1)
+      hipExtLaunchKernelGGL(kern, grid, block, 0, s, e0, e1, 0, T);
+    else
+      hipLaunchKernelGGL(kern, grid, block, 0, s, T);
+  };
+  band ? launch(k_encode420_slots_batch<true>) : launch(k_encode420_slots_batch<false>);
+  return check_launch("k_encode420_slots_batch");
 }
 
 extern "C" int hic_probe_encode420(const uint8_t *rgb, int64_t H, int64_t W, int16_t *coef_y, int16_t *coef_cr,

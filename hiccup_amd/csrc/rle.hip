@@ -22,10 +22,15 @@
 // Sharding: the same kernels take a carry (zeros preceding the shard since the
 // last nonzero of earlier shards), the previous shard's last DC, and whether this
 // shard closes the stream (EOB) -- see hic_rle_stitch.
+#include <algorithm>
 #include <atomic>
 #include <climits>
+#include <cstring>
+#include <utility>
+#include <vector>
 
 #include "rle_core.h"
+#include "slots_batch.h"
 
 namespace hic {
 namespace {
@@ -1770,6 +1775,180 @@ __global__ __launch_bounds__(256) void k_rld_indexed16(const uint8_t *__restrict
   }
 }
 
+
+// The close of a batch of slot-layout images (hic_rle_slots_close_batch, slots_batch.h):
+// all 3 n channels in one launch.  The images share a shape, so workgroup -> (image,
+// channel, partition) is arithmetic; the job comes from the image's table entry.
+// A partition's hand-offs look back only to earlier partitions of its own channel,
+// which have smaller workgroup indices, and workgroups are dispatched in index order:
+// whatever a partition waits for is resident or done, so a grid larger than the
+// resident set cannot deadlock -- and the spin is bounded in any case (the failure
+// granule, folded into the count by k_rle_scan_fold_table).
+// The body is k_rle_scan16b<true>'s, written out again and not shared: with the body
+// in a __device__ function both callers inline, the existing instantiations' register
+// allocation changed (tools/check/kernel_isa_diff.py), and they are to stay as they are.
+struct ScanTable {
+  const SlotBatchEntry *tab;
+  int64_t nblk[3];
+  int nrec[3], parts[3];
+  int parts_image, n, M;
+  uint32_t epoch;
+};
+// (templates only so that they are instantiated, and so emitted, after every existing
+// kernel: the block labels of those then keep their numbers in the listing)
+template <int = 0>
+__global__ __launch_bounds__(kScan16T) void k_rle_scan16_table(ScanTable T) {
+  __shared__ Agg s_wave[kScan16T / 64 + 1];
+  __shared__ Agg s_pre;
+  __shared__ int s_fail;
+  // workgroup -> (image, channel, partition)
+  const int b = (int)blockIdx.x, img = b / T.parts_image;
+  int pp = b - img * T.parts_image, ch = 0;
+  if (pp >= T.parts[0]) {
+    pp -= T.parts[0];
+    ch = 1;
+    if (pp >= T.parts[1]) {
+      pp -= T.parts[1];
+      ch = 2;
+    }
+  }
+  const int64_t p = pp;
+  const SlotBatchChan &c = T.tab[img].c[ch];
+  struct {
+    int64_t nrec, nblk, bpr, cap;
+    int64_t *ws, *d_count;
+    uint8_t *slot_len, *sym_len;
+    int16_t *sym_val;
+    int32_t *dc_diff, *rdc, *sidx;
+  } const J{T.nrec[ch], T.nblk[ch], ch ? 32 : 64, c.cap, c.ws, c.d_count, c.slot_len, c.sym_len,
+            c.sym_val, c.dc_diff, c.rdc, c.sidx};
+  const int M = T.M;
+  const uint32_t epoch = T.epoch;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t nt = J.nrec, np = (nt + kScan16T - 1) / kScan16T;
+  const int64_t *tiles = J.ws;
+  int64_t *offs = J.ws + rle_offs_word(nt);
+  uint64_t *gran = reinterpret_cast<uint64_t *>(J.ws + 5 * nt);  // 3 per partition
+  const uint32_t tag = (epoch << 2) | 1u;
+  const int64_t t = p * kScan16T + threadIdx.x;
+  const Agg rec = t < nt ? Agg{tiles[t * 3 + 0], tiles[t * 3 + 1], tiles[t * 3 + 2]} : Agg{-1, -1, 0};
+  // workgroup inclusive scan of the partition's tile records
+  Agg incl = rec;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const Agg o = agg_shfl_up(incl, d);
+    if (lane >= d) incl = agg_combine(o, incl, M);
+  }
+  if (lane == 63) s_wave[wave] = incl;
+  if (threadIdx.x == 0) s_fail = 0;
+  __syncthreads();
+  if (wave == 0) {
+    constexpr int NW = kScan16T / 64;
+    Agg it = lane < NW ? s_wave[lane] : Agg{-1, -1, 0};
+#pragma unroll
+    for (int d = 1; d < NW; d <<= 1) {
+      const Agg o = agg_shfl_up(it, d);
+      if (lane >= d) it = agg_combine(o, it, M);
+    }
+    Agg ex = agg_shfl_up(it, 1);
+    if (lane == 0) ex = Agg{-1, -1, 0};
+    if (lane < NW) s_wave[lane] = ex;
+    if (lane == NW - 1) {
+      s_wave[NW] = it;  // the partition's aggregate: publish it
+      put_granule(gran + 3 * p + 0, it.first, tag);
+      put_granule(gran + 3 * p + 1, it.last, tag);
+      put_granule(gran + 3 * p + 2, it.cnt, tag);
+    }
+    // fold the aggregates of the earlier partitions (lane q < p polls partition q)
+    Agg pre{-1, -1, 0};
+    for (int64_t q0 = 0; q0 < p; q0 += 64) {
+      const int64_t q = q0 + lane;
+      Agg a{-1, -1, 0};
+      if (q < p) {
+        bool ok = false;
+        for (int spin = 0; spin < (1 << 22) && !ok; ++spin) {
+          int64_t f, l, c;
+          ok = (int)get_granule(gran + 3 * q + 0, tag, f) & (int)get_granule(gran + 3 * q + 1, tag, l) &
+               get_granule(gran + 3 * q + 2, tag, c);
+          if (ok) a = Agg{f, l, c};
+          else __builtin_amdgcn_s_sleep(2);
+        }
+        if (!ok) s_fail = 1;
+      }
+      // the window's ordered total by a wave scan (agg_combine is associative):
+      // log2(64) steps instead of one serial combine per earlier partition (the
+      // 16K image has 512 partitions per channel, and its last ones folded them all)
+      Agg wi = a;
+#pragma unroll
+      for (int d = 1; d < 64; d <<= 1) {
+        const Agg o = agg_shfl_up(wi, d);
+        if (lane >= d) wi = agg_combine(o, wi, M);
+      }
+      const int lastl = (int)(p - q0 < 64 ? p - q0 - 1 : 63);
+      pre = agg_combine(pre, Agg{__shfl(wi.first, lastl, 64), __shfl(wi.last, lastl, 64), __shfl(wi.cnt, lastl, 64)}, M);
+    }
+    if (lane == 0) s_pre = pre;
+  }
+  __syncthreads();
+  const int64_t p0 = -1;  // virtual last nonzero before the stream (a whole image: no carry)
+  Agg excl = agg_shfl_up(incl, 1);
+  if (lane == 0) excl = Agg{-1, -1, 0};
+  excl = agg_combine(agg_combine(s_pre, s_wave[wave], M), excl, M);
+  if (t < nt) {
+    offs[t * 2 + 0] = excl.last >= 0 ? excl.cnt + syms_for_run(excl.first - p0 - 1, M) : 0;
+    offs[t * 2 + 1] = excl.last >= 0 ? excl.last : p0;
+  }
+  if (t < nt) {
+    // the record's first nonzero continues the zero run since the previous record's
+    // last nonzero: its fillers and its first symbol's length (written as 0 by the
+    // fused kernel); P: the record-relative position the run's remainder starts after
+    const int64_t prv = excl.last >= 0 ? excl.last : p0, capr = 63 * J.bpr;
+    int n = 0, P = 0, nf = 0;
+    if (rec.first >= 0) {
+      const int64_t run = rec.first - prv - 1, f = div_run(run, M);
+      const int len0 = (int)(run - f * M);
+      nf = (int)f;
+      n = (int)rec.cnt + 1;
+      P = (int)(rec.first - t * capr) - len0;
+      J.slot_len[t * capr] = (uint8_t)len0;
+    }
+    // codec.differential_coding across the record boundary
+    const int pdc = t > 0 ? J.rdc[t - 1] : 0;
+    if (t > 0) J.dc_diff[t * J.bpr] -= pdc;
+    *reinterpret_cast<int4 *>(J.sidx + 4 * t) = make_int4(n, P, pdc, nf);
+  }
+  if (p == np - 1 && threadIdx.x == 0) {  // the channel's last partition closes the stream
+    const Agg all = agg_combine(s_pre, s_wave[kScan16T / 64], M);
+    const int64_t last = all.last >= 0 ? all.last : p0;
+    const int64_t n_ac = J.nblk * 63;
+    int64_t total = all.last >= 0 ? all.cnt + syms_for_run(all.first - p0 - 1, M) : 0;
+    if (!(n_ac > 0 && last == n_ac - 1)) {
+      if (total < J.cap) {
+        J.sym_len[total] = 0;
+        J.sym_val[total] = 0;
+      }
+      ++total;
+    }
+    *J.d_count = total <= J.cap ? total : -total;
+  }
+  // a hand-off that timed out is reported, not waited for: a tagged failure granule
+  // after the partitions' ones, folded into *d_count by the emit (which runs after
+  // every partition's write, so the report cannot be overwritten by a total)
+  if (s_fail && threadIdx.x == 0) put_granule(gran + 3 * np, 1, tag);
+}
+// k_rle_scan_fold for the table: thread -> (image, channel)
+template <int = 0>
+__global__ __launch_bounds__(256) void k_rle_scan_fold_table(ScanTable T) {
+  const int t = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (t >= 3 * T.n) return;
+  const int img = t / 3, ch = t - 3 * img;
+  const SlotBatchChan &c = T.tab[img].c[ch];
+  const int64_t nrec = T.nrec[ch];
+  int64_t f;
+  if (get_granule(reinterpret_cast<const uint64_t *>(c.ws + 5 * nrec) + 3 * T.parts[ch], (T.epoch << 2) | 1u, f))
+    *c.d_count = HIC_COUNT_SCAN_TIMEOUT;
+}
+
 }  // namespace
 }  // namespace hic
 
@@ -2041,6 +2220,143 @@ extern "C" int hic_rle_slots_close(int n, const hic_slot_job *jobs, int max_len,
   if (int e = scan_batch16<true>(J, s)) return e;
   hipLaunchKernelGGL(k_rle_scan_fold, dim3(1), dim3(64), 0, s, J);
   return check_launch("k_rle_scan_fold");
+}
+
+// ---- the batched slot encode's table (slots_batch.h) ----
+// the header of n images of H x W; nullptr = good, else what the shape lacks
+static const char *slot_batch_header(int n, int64_t H, int64_t W, SlotBatchHeader &h) {
+  if (n < 1 || n > HIC_SLOTS_BATCH_MAX) return "1 <= n <= HIC_SLOTS_BATCH_MAX images";
+  if (H < 16 || W < 512 || H % 16 || W % 512 || H >= (1 << 20) || W >= (1 << 20))
+    return "the slot layout needs W % 512 == 0 and H % 16 == 0";
+  if (H * W * 3 > INT32_MAX) return "image exceeds 2 GiB (32-bit buffer offsets)";
+  h = SlotBatchHeader{};
+  h.magic = kSlotBatchMagic;
+  h.n = n;
+  h.max_len = 15;
+  h.H = H;
+  h.W = W;
+  h.nstrips = (int32_t)(W / 512);
+  h.nunits = (int32_t)(h.nstrips * (H / 16));
+  h.wg_band = (int32_t)(((H / 16 + HIC_ENC_WPB - 1) / HIC_ENC_WPB) * h.nstrips);
+  h.wg_flat = (h.nunits + HIC_ENC_WPB - 1) / HIC_ENC_WPB;
+  for (int k = 0; k < 3; ++k) {
+    h.nblk[k] = k ? (H / 16) * (W / 16) : (H / 8) * (W / 8);
+    h.nrec[k] = (int32_t)slot_nrec(h.nblk[k], k ? 2 : 1);
+    h.parts[k] = (h.nrec[k] + kScan16T - 1) / kScan16T;
+    h.parts_image += h.parts[k];
+  }
+  // the flattened grids (wg_band >= wg_flat's waves / HIC_ENC_WPB) and unit counts in 32 bits
+  if ((int64_t)n * h.wg_band * HIC_ENC_WPB > INT32_MAX / 64 || (int64_t)n * h.parts_image > INT32_MAX / 64)
+    return "too many units in the batch";
+  return nullptr;
+}
+
+namespace hic {
+const char *slot_batch_header_error(const SlotBatchHeader &h) {
+  if (h.magic != kSlotBatchMagic) return "not a batch table (magic)";
+  SlotBatchHeader want;
+  if (const char *e = slot_batch_header(h.n, h.H, h.W, want)) return e;
+  return memcmp(&want, &h, sizeof want) ? "damaged batch table header" : nullptr;
+}
+}  // namespace hic
+
+extern "C" size_t hic_slots_batch_table_bytes(int n) {
+  if (n < 1 || n > HIC_SLOTS_BATCH_MAX) return 0;
+  return sizeof(SlotBatchHeader) + (size_t)n * sizeof(SlotBatchEntry);
+}
+
+extern "C" int hic_slots_batch_table(int n, int64_t H, int64_t W, const hic_slot_job *jobs, void *h_table,
+                                     size_t table_bytes) {
+  SlotBatchHeader h;
+  if (const char *e = slot_batch_header(n, H, W, h)) return arg_error(e);
+  if (!jobs || !h_table) return arg_error("null pointer");
+  if (table_bytes < hic_slots_batch_table_bytes(n))
+    return arg_error("table of %lld bytes, %lld needed", (long long)table_bytes,
+                     (long long)hic_slots_batch_table_bytes(n));
+  // every job checked before a byte is written: what hic_encode420_slots_u8 and
+  // hic_rle_slots_close check of theirs
+  for (int i = 0; i < 3 * n; ++i) {
+    const hic_slot_job &a = jobs[i];
+    const int k = i % 3, rpt = k ? 2 : 1;
+    if (!a.slot_len || !a.slot_val || !a.dc_diff || !a.d_index || !a.workspace || !a.d_count || !a.sym_len ||
+        !a.sym_val)
+      return arg_error("image %d job %d: null pointer", i / 3, k);
+    if (a.nblk != h.nblk[k] || a.records_per_tile != rpt)
+      return arg_error("image %d job %d: nblk %lld / records_per_tile %lld, expected %lld / %d", i / 3, k,
+                       (long long)a.nblk, (long long)a.records_per_tile, (long long)h.nblk[k], rpt);
+    if (a.nblk > (int64_t)INT32_MAX / 63) return arg_error("image %d job %d: nblk", i / 3, k);
+    if ((reinterpret_cast<uintptr_t>(a.slot_len) | reinterpret_cast<uintptr_t>(a.slot_val)) % 16)
+      return arg_error("image %d job %d: slot arrays must be 16-byte aligned", i / 3, k);
+    const int64_t need = (int64_t)hic_rle_slots_workspace_bytes(a.nblk, rpt);
+    if (a.workspace_bytes < need)
+      return arg_error("image %d job %d: workspace of %lld bytes, %lld needed", i / 3, k,
+                       (long long)a.workspace_bytes, (long long)need);
+  }
+  // no two jobs may share what the launches write per job: sorted by address, a
+  // range must end before the next one starts
+  {
+    std::vector<std::pair<uintptr_t, uintptr_t>> r((size_t)3 * n);
+    const char *what[4] = {"slot_len", "slot_val", "dc_diff", "workspace"};
+    for (int w = 0; w < 4; ++w) {
+      for (int i = 0; i < 3 * n; ++i) {
+        const hic_slot_job &a = jobs[i];
+        const void *p = w == 0 ? (const void *)a.slot_len : w == 1 ? (const void *)a.slot_val
+                        : w == 2 ? (const void *)a.dc_diff : (const void *)a.workspace;
+        const int64_t bytes = w == 0 ? a.nblk * 63 : w == 1 ? a.nblk * 126 : w == 2 ? a.nblk * 4
+                              : (int64_t)hic_rle_slots_workspace_bytes(a.nblk, (int)a.records_per_tile);
+        r[i] = {reinterpret_cast<uintptr_t>(p), (uintptr_t)bytes};
+      }
+      std::sort(r.begin(), r.end());
+      for (size_t i = 0; i + 1 < r.size(); ++i)
+        if (r[i].first + r[i].second > r[i + 1].first) return arg_error("two jobs share a %s range", what[w]);
+    }
+  }
+  memcpy(h_table, &h, sizeof h);
+  SlotBatchEntry *ent = reinterpret_cast<SlotBatchEntry *>(static_cast<char *>(h_table) + sizeof h);
+  for (int i = 0; i < n; ++i) {
+    SlotBatchEntry e{};
+    for (int k = 0; k < 3; ++k) {
+      const hic_slot_job &a = jobs[3 * i + k];
+      SlotBatchChan &c = e.c[k];
+      c.slot_len = a.slot_len;
+      c.slot_val = a.slot_val;
+      c.dc_diff = a.dc_diff;
+      c.ws = static_cast<int64_t *>(a.workspace);
+      c.rdc = reinterpret_cast<int32_t *>(c.ws + rle_ws_words(h.nrec[k]));
+      c.sidx = a.d_index;
+      c.d_count = a.d_count;
+      c.sym_len = a.sym_len;
+      c.sym_val = a.sym_val;
+      c.cap = a.sym_cap;
+    }
+    memcpy(ent + i, &e, sizeof e);
+  }
+  return HIC_OK;
+}
+
+extern "C" int hic_rle_slots_close_batch(const void *h_table, const void *d_table, int max_len, void *stream) {
+  if (!h_table || !d_table) return arg_error("null pointer");
+  if (max_len != 15) return arg_error("the slot layout needs max_len 15");
+  if (reinterpret_cast<uintptr_t>(d_table) % 16) return arg_error("d_table must be 16-byte aligned");
+  SlotBatchHeader h;
+  memcpy(&h, h_table, sizeof h);
+  if (const char *e = slot_batch_header_error(h)) return arg_error(e);
+  ScanTable T{};
+  T.tab = reinterpret_cast<const SlotBatchEntry *>(static_cast<const char *>(d_table) + sizeof h);
+  for (int k = 0; k < 3; ++k) {
+    T.nblk[k] = h.nblk[k];
+    T.nrec[k] = h.nrec[k];
+    T.parts[k] = h.parts[k];
+  }
+  T.parts_image = h.parts_image;
+  T.n = h.n;
+  T.M = max_len;
+  T.epoch = next_epoch();
+  hipStream_t s = as_stream(stream);
+  hipLaunchKernelGGL(k_rle_scan16_table<>, dim3((unsigned)(h.n * h.parts_image)), dim3(kScan16T), 0, s, T);
+  if (int e = check_launch("k_rle_scan16_table")) return e;
+  hipLaunchKernelGGL(k_rle_scan_fold_table<>, dim3((unsigned)((3 * h.n + 255) / 256)), dim3(256), 0, s, T);
+  return check_launch("k_rle_scan_fold_table");
 }
 
 extern "C" int hic_rle_slots_compact(int n, const hic_slot_job *jobs, int max_len, void *stream) {

@@ -401,10 +401,12 @@ class Encoder:
         with device.on_stream(stream):  # the counts and histograms are read after the stream's kernels
             return self._hic_image(stream, from_slots)
 
-    def _hic_image(self, stream, from_slots):
+    def _hic_image(self, stream, from_slots, counts=None):
+        """counts: the three symbol counts when the caller has already read them
+        (BatchEncoder.hic_images: one read for the batch)."""
         from . import hicimage as hic
         from . import huffman
-        counts = self.counts.cpu().tolist()
+        counts = self.counts.cpu().tolist() if counts is None else counts
         jobs = self._slot_jobs() if from_slots else None
         keys = {}
         for i, k in enumerate(CHANNELS):
@@ -471,6 +473,103 @@ def transform_batch(encoders, inputs, stream=None, in_row0s=None, dct_events=Non
     _lib.call("hic_encode420_batch_u8", n, jobs, encoders[0].max_len, s, *first)
     for ev in evs[1:]:
         _lib.call("hic_event_record", ev.stop, s)
+
+
+BATCH_MAX = 4096  # HIC_SLOTS_BATCH_MAX (include/hiccup_hip.h)
+
+
+def batch_slots_eligible(n, H, W, max_len=15):
+    """Whether BatchEncoder takes n images of H x W: 1 <= n <= BATCH_MAX whole images
+    that slots_eligible accepts, their units together within the flattened grid's
+    32-bit count (hic_slots_batch_table's limits)."""
+    if not (1 <= n <= BATCH_MAX and slots_eligible(H, W, max_len)):
+        return False
+    bands = -(-(H // 16) // 4) * (W // 512)
+    parts = sum(-(-(_nblk(h, w) // b) // 256) for h, w, b in ((H, W, 64), (H // 2, W // 2, 32), (H // 2, W // 2, 32)))
+    return n * bands * 4 <= (2**31 - 1) // 64 and n * parts <= (2**31 - 1) // 64
+
+
+class BatchEncoder:
+    """n images of one shape in the slot layout, encoded by ONE fused launch
+    (hic_encode420_slots_batch_u8) and closed by ONE scan launch
+    (hic_rle_slots_close_batch) instead of two launches per image: a 512 x 512 image
+    is 8 workgroups of the fused kernel, and a run of such launches is bound by
+    launch latency.  The batch holds n ordinary Encoder(H, W, slots=True) objects
+    (batch[i], len(batch)) whose buffers the batched launches write, so everything
+    after the close is an Encoder's, per image: batch[i].index for Decoder.decode,
+    compact(), materialize(), result(), hic_image(from_slots=True).  Per image the
+    results are bit for bit those of Encoder(H, W).encode."""
+
+    def __init__(self, n, H, W):
+        if not batch_slots_eligible(n, H, W):
+            raise ValueError("a batch needs 1 <= n <= %d whole images with W %% 512 == 0 and H %% 16 == 0"
+                             % BATCH_MAX)
+        device.require_gpu()
+        self.n, self.H, self.W = n, H, W
+        self.encoders = [Encoder(H, W, slots=True) for _ in range(n)]
+        # one counts tensor: each encoder's counts is a view of its row (one host read
+        # checks the batch)
+        self.counts = device.zeros((n, 3), torch.int64)
+        for i, e in enumerate(self.encoders):
+            e.counts = self.counts[i]
+        # the per-batch table (hic_slots_batch_table): built on the host and uploaded once
+        lib = _lib.load()
+        jobs = (_lib.SlotJob * (3 * n))()
+        for i, e in enumerate(self.encoders):
+            for k, j in enumerate(e._slot_jobs()):
+                jobs[3 * i + k] = j
+        nbytes = lib.hic_slots_batch_table_bytes(n)
+        self._h_table = ctypes.create_string_buffer(nbytes)
+        _lib.call("hic_slots_batch_table", n, H, W, jobs, self._h_table, nbytes)
+        self._d_table = device.to_device(np.frombuffer(self._h_table, np.uint8, nbytes))
+
+    def __len__(self):
+        return self.n
+
+    def __getitem__(self, i):
+        return self.encoders[i]
+
+    def _stride(self, rgb):
+        """The byte stride between images of an (n, H, W, 3) uint8 device tensor."""
+        n, H, W = self.n, self.H, self.W
+        if not (isinstance(rgb, torch.Tensor) and rgb.is_cuda and rgb.dtype == torch.uint8
+                and tuple(rgb.shape) == (n, H, W, 3)):
+            raise ValueError("a batch takes an (%d, %d, %d, 3) uint8 device tensor" % (n, H, W))
+        if tuple(rgb.stride()[1:]) != (3 * W, 3, 1):
+            raise ValueError("each image of the batch must be contiguous")
+        stride = rgb.stride(0) if n > 1 else H * W * 3  # (a size-1 dimension's stride means nothing)
+        if stride < H * W * 3 or stride % 8:
+            raise ValueError("the images' stride must be >= H * W * 3 and a multiple of 8 (got %d)" % stride)
+        return stride
+
+    def transform(self, rgb, stream=None, dct_events=None):
+        """Encoder.transform of all n images: one launch (dct_events time it)."""
+        stride = self._stride(rgb)
+        ev = (dct_events.start, dct_events.stop) if dct_events is not None else (None, None)
+        _lib.call("hic_encode420_slots_batch_u8", device.ptr(rgb), stride, self._h_table, device.ptr(self._d_table),
+                  15, device.stream_ptr(stream), *ev)
+
+    def entropy(self, stream=None):
+        """Encoder.entropy of all n images: the close of their 3 n channels in one scan launch."""
+        _lib.call("hic_rle_slots_close_batch", self._h_table, device.ptr(self._d_table), 15,
+                  device.stream_ptr(stream))
+
+    def encode(self, rgb, stream=None, dct_events=None):
+        self.transform(rgb, stream, dct_events=dct_events)
+        self.entropy(stream)
+
+    def hic_images(self, stream=None, from_slots=True):
+        """[batch[i].hic_image(stream, from_slots)]: one read of the batch's counts, then
+        the per-image Huffman stage (nine trees per image on the host; syncs)."""
+        if not from_slots:
+            for e in self.encoders:
+                e.compact(stream)
+        with device.on_stream(stream):
+            counts = self.counts.cpu().tolist()
+            for c in counts:
+                for v, k in zip(c, CHANNELS):
+                    check_count(int(v), k)
+            return [e._hic_image(stream, bool(from_slots), counts[i]) for i, e in enumerate(self.encoders)]
 
 
 class Decoder:

@@ -243,6 +243,35 @@ int hic_encode420_slots_u8(const uint8_t *rgb, int64_t H, int64_t W, const hic_s
                            void *stream, void *ev_start, void *ev_stop);
 int hic_rle_slots_close(int n, const hic_slot_job *jobs, int max_len, void *stream);
 int hic_rle_slots_compact(int n, const hic_slot_job *jobs, int max_len, void *stream);
+/* ---- batched slot encode (round 12): n images of ONE shape, each a whole image the
+ *      slot layout takes (W % 512 == 0, H % 16 == 0, max_len 15), encoded by one fused
+ *      launch and closed by one scan launch; per image the results are exactly those
+ *      of hic_encode420_slots_u8 + hic_rle_slots_close.  A 512 x 512 image is 8
+ *      workgroups of the fused kernel: alone it is bound by launch latency.
+ *  The 30 per-image kernel arguments live in a table in device memory.  The library
+ *  allocates nothing: hic_slots_batch_table fills a host blob of
+ *  hic_slots_batch_table_bytes(n) bytes (0 unless 1 <= n <= HIC_SLOTS_BATCH_MAX), the
+ *  caller copies it to the device once (16-byte aligned) and passes both copies to
+ *  every launch: h_table is read on the host (magic, n, H, W, the grids; a foreign or
+ *  damaged blob is HIC_ERR_ARG before any launch), d_table by the kernels.
+ *  hic_slots_batch_table: jobs[3 i .. 3 i + 2] = image i's Y, Cr, Cb, each checked as
+ *    hic_encode420_slots_u8 and hic_rle_slots_close check theirs, every one before a
+ *    byte is written; also refused: n outside 1 .. HIC_SLOTS_BATCH_MAX, more units or
+ *    scan partitions than INT32_MAX / 64, a table_bytes below the blob's size, and
+ *    two jobs whose slot_len, slot_val, dc_diff or workspace ranges overlap.
+ *  hic_encode420_slots_batch_u8: image i's H x W x 3 bytes start at rgb + i *
+ *    image_stride (image_stride >= H * W * 3 and a multiple of 8, rgb 8-byte aligned;
+ *    the 2 GiB limit of the 32-bit buffer offsets holds per image, not for the
+ *    batch).  Knobs HIC_KNOB_ENCODE_BAND / _ORDER and the events as in
+ *    hic_encode420_slots_u8.
+ *  hic_rle_slots_close_batch: hic_rle_slots_close of all 3 n channels in one scan
+ *    launch (and one small launch folding timed-out hand-offs into the counts). */
+#define HIC_SLOTS_BATCH_MAX 4096
+size_t hic_slots_batch_table_bytes(int n);
+int hic_slots_batch_table(int n, int64_t H, int64_t W, const hic_slot_job *jobs, void *h_table, size_t table_bytes);
+int hic_encode420_slots_batch_u8(const uint8_t *rgb, int64_t image_stride, const void *h_table, const void *d_table,
+                                 int max_len, void *stream, void *ev_start, void *ev_stop);
+int hic_rle_slots_close_batch(const void *h_table, const void *d_table, int max_len, void *stream);
 /* The Huffman stage's key range, histogram and bit packing (hic_key_range /
  * hic_key_histogram / hic_huffman_pack below) read straight from the slot layout,
  * after hic_rle_slots_close and with no hic_rle_slots_compact: results are exactly
