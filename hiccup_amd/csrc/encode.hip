@@ -709,10 +709,31 @@ __device__ __forceinline__ int enc_unit_of(const Enc420 &E, int bx, int wv) {
   return __builtin_amdgcn_readfirstlane((band * HIC_ENC_WPB + wv) * E.nstrips + s);
 }
 
+// A slot kernel's LDS, one block so that the order is fixed: the waves' 4 KiB chroma
+// areas, then their stages -- slot_pass (slots.h) needs every stage at least
+// kSlotStageMin bytes into the workgroup's LDS.
+struct alignas(16) EncSlotLds {
+  uint32_t chroma[HIC_ENC_WPB][2 * 8 * 64];
+  uint2 stage[HIC_ENC_WPB * 64 * kStageU2];
+};
+static_assert(offsetof(EncSlotLds, stage) >= kSlotStageMin && offsetof(EncSlotLds, stage) % 16 == 0,
+              "slot_pass: the stage lies kSlotStageMin bytes into LDS, 16-byte aligned");
+static_assert(sizeof(EncSlotLds) == 51200, "3 workgroups per CU: 3 waves per SIMD");
+
 template <int TMF, bool SLOTS = false, bool BAND = false>
 __global__ __launch_bounds__(64 * HIC_ENC_WPB) __attribute__((amdgpu_waves_per_eu(3))) void k_encode420(Enc420 E) {
-  __shared__ __attribute__((aligned(16))) uint2 s_stage[HIC_ENC_WPB * 64 * kStageU2];
-  __shared__ uint32_t s_chroma_all[HIC_ENC_WPB][2 * 8 * 64];
+  uint2 *s_stage;
+  uint32_t(*s_chroma_all)[2 * 8 * 64];
+  if constexpr (SLOTS) {
+    __shared__ EncSlotLds s_lds;
+    s_stage = s_lds.stage;
+    s_chroma_all = s_lds.chroma;
+  } else {
+    __shared__ __attribute__((aligned(16))) uint2 s_stage_[HIC_ENC_WPB * 64 * kStageU2];
+    __shared__ uint32_t s_chroma_[HIC_ENC_WPB][2 * 8 * 64];
+    s_stage = s_stage_;
+    s_chroma_all = s_chroma_;
+  }
   const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int bx = __builtin_amdgcn_readfirstlane(E.xcd ? xcd_block((int)blockIdx.x, (int)gridDim.x) : (int)blockIdx.x);
   const int g = enc_unit_of<BAND>(E, bx, wv);
@@ -766,8 +787,9 @@ struct Enc420Table {
 template <bool BAND>
 __global__ __launch_bounds__(64 * HIC_ENC_WPB) __attribute__((amdgpu_waves_per_eu(3))) void k_encode420_slots_batch(
     Enc420Table T) {
-  __shared__ __attribute__((aligned(16))) uint2 s_stage[HIC_ENC_WPB * 64 * kStageU2];
-  __shared__ uint32_t s_chroma_all[HIC_ENC_WPB][2 * 8 * 64];
+  __shared__ EncSlotLds s_lds;
+  uint2 *s_stage = s_lds.stage;
+  auto &s_chroma_all = s_lds.chroma;
   const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int bf = __builtin_amdgcn_readfirstlane(T.xcd ? xcd_block((int)blockIdx.x, (int)gridDim.x) : (int)blockIdx.x);
   const int img = __builtin_amdgcn_readfirstlane(bf / T.wpi), bx = __builtin_amdgcn_readfirstlane(bf - img * T.wpi);

@@ -61,6 +61,36 @@ typedef short i16x2_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ uint32_t lds_addr(const void *p) {
   return (uint32_t)(uintptr_t)(const lds_u16 *)reinterpret_cast<const uint16_t *>(p);
 }
+// a * b + c on signed 24-bit a, b (v_mad_i32_i24, full rate)
+__device__ __forceinline__ int mad_i24(int a, int b, int c) { return __mul24(a, b) + c; }
+// a - 2 z for a flag z (0 / 1) in that one instruction (the compiler makes a shift
+// and a subtract of the multiply by the constant)
+__device__ __forceinline__ uint32_t sub_2z(uint32_t a, int z) {
+#ifdef __HIP_DEVICE_COMPILE__
+  asm("v_mad_i32_i24 %0, %1, -2, %0" : "+v"(a) : "v"(z));
+  return a;
+#else
+  return a - 2u * (uint32_t)z;
+#endif
+}
+// The packed word of a coefficient in a dword's high half, (w >> 16) * 16 + len, in
+// one instruction (a 16-bit multiply-add on the selected half): its low 16 bits are
+// ((w >> 12) & 0xFFF0) | len for every len < 16, which covers every word that is kept
+// (their len is 0 .. 14).
+__device__ __forceinline__ uint32_t pack_hi16(uint32_t w, uint32_t len) {
+#ifdef __HIP_DEVICE_COMPILE__
+  uint32_t r;
+  asm("v_mad_u32_u16 %0, %1, 16, %2 op_sel:[1,0,0,0]" : "=v"(r) : "v"(w), "v"(len));
+  return r;
+#else
+  return (w >> 16) * 16u + len;
+#endif
+}
+// slot_pass's emission keeps a lane's store address less twice the coefficient index
+// in a register (up to 124 bytes below the lane's first slot): a stage handed to it
+// starts at least this many bytes into the workgroup's LDS, so that register never
+// goes below zero.
+constexpr int kSlotStageMin = 128;
 
 // The symbols of a lane's block after its first nonzero (plus, for a lane that
 // does not hold its record's first nonzero, the fillers of the zero run carried in
@@ -193,6 +223,13 @@ __device__ __forceinline__ void slot_pass(const uint32_t (&zw)[32], uint2 *st2, 
     __builtin_amdgcn_wave_barrier();
     return;
   }
+  // What the code after the loop needs of the summary, in two registers instead of
+  // four across the loop (the loop holds two masks and a flag the compare form did
+  // not; without this the row-major kernels spill one dword more): the first symbol's
+  // word, whose low nibble is rem, and nf0 << 8 | (first & 0xFF).
+  const uint32_t wfirst = ((uint32_t)vfirst << 4) | (uint32_t)rem;
+  uint32_t fn = ((uint32_t)nf0 << 8) | ((uint32_t)first & 0xFFu);
+  const int c0 = rem - first;
   // ---- 3. packed symbols into the stage, in place
   uint16_t *sb = reinterpret_cast<uint16_t *>(st2) + (hi ? 32 * kStageRowU16 : 0);
   {
@@ -203,31 +240,50 @@ __device__ __forceinline__ void slot_pass(const uint32_t (&zw)[32], uint2 *st2, 
     // below, after the loop, where every lane writes its carried fillers and its
     // first symbol again.  A block with a run >= 15 inside (not dense) writes within
     // its own symbols here, and the general loop after writes them all.
-    uint32_t la = lds_addr(sb + o + nf0);
-    int pl = first - 1 - rem;
+    //
+    // The two loop-carried values are one multiply-add each on the coefficient's zero
+    // flag z (a bit of ~ev / ~od: no compare, no VCC), off the flags' own chain:
+    //   c_j = j - pl_j - 1, the zeros since the last nonzero (pl: its index; before
+    //         the first one first - 1 - rem, so c_0 = rem - first, negative when the
+    //         block starts with more zeros than the carried run): the word's length.
+    //         c_{j+1} = z_j * c_j + z_j, signed, in [-63, 77].
+    //   a_j = (the lane's next free slot's address) - 2j, the store at a_j + 2j with 2j
+    //         in the instruction's offset: a_{j+1} = a_j - 2 z_j >= a_0 - 124, which
+    //         never goes below zero because the stage starts kSlotStageMin bytes into
+    //         the workgroup's LDS (every kernel that calls slot_pass carves it so).
+    const uint32_t zev = ~ev, zod = ~od;
+    uint32_t a = lds_addr(sb + o + nf0);
+    int c = c0;
     // AC j is zig-zag slot j + 1: the low half of zw[(j + 1) / 2] for odd j, the
     // high half for even j.  The packed word is formed without extracting the value:
-    // low half, (w << 4) | len (the store keeps 16 bits); high half, (w >> 12) with
-    // its low nibble replaced by len.
+    // low half, (w << 4) | len (the store keeps 16 bits); high half, pack_hi16.  (A
+    // kept word has len in 0 .. 14; pack_hi16 is exact for every len < 16.  A word
+    // whose len lies outside -- before the first nonzero, or in a block that is not
+    // dense -- is one of those written again below.)
 #pragma unroll
     for (int j = 0; j < 63; ++j) {
       const uint32_t w = zw[(j + 1) >> 1];
       const bool lo = ((j + 1) & 1) == 0;
-      const bool nz = lo ? (uint16_t)w != 0 : w > 0xFFFFu;
-      const uint32_t len = (uint32_t)(j - pl - 1);
-      const uint32_t pk = lo ? ((w << 4) | len) : (((w >> 12) & 0xFFF0u) | len);
-      *(lds_u16 *)(uintptr_t)la = (uint16_t)pk;
-      la += nz ? 2u : 0u;
-      pl = nz ? j : pl;
+      const int z = (int)__builtin_amdgcn_ubfe(lo ? zev : zod, (uint32_t)((j + 1) >> 1), 1u);
+      const uint32_t len = (uint32_t)c;
+      const uint32_t pk = lo ? ((w << 4) | len) : pack_hi16(w, len);
+      *(lds_u16 *)(uintptr_t)(a + 2u * (uint32_t)j) = (uint16_t)pk;
+      a = sub_2z(a, z);
+      c = mad_i24(z, c, z);
     }
   }
   __builtin_amdgcn_wave_barrier();
-  if (first >= 0) {
-    for (int k = 0; k < nf0; ++k) sb[o + k] = (uint16_t)(kSlotM - 1);
-    sb[o + nf0] = (uint16_t)(((uint32_t)vfirst << 4) | (uint32_t)rem);
+#ifdef __HIP_DEVICE_COMPILE__
+  asm volatile("" : "+v"(fn));  // opaque, or the compiler keeps first and nf0 live instead
+#endif
+  const int first2 = (int)(int8_t)(fn & 0xFFu), nf02 = (int)(fn >> 8);  // = first, nf0
+  if (first2 >= 0) {
+    for (int k = 0; k < nf02; ++k) sb[o + k] = (uint16_t)(kSlotM - 1);
+    sb[o + nf02] = (uint16_t)wfirst;
   }
-  if (__builtin_expect(__builtin_amdgcn_ballot_w64(!dense && first >= 0) != 0, 0)) {
-    if (!dense && first >= 0) slot_block_packed(HIC_SLOT_Z32(zw), first, o, nf0, rem, lds_addr(sb));
+  if (__builtin_expect(__builtin_amdgcn_ballot_w64(!dense && first2 >= 0) != 0, 0)) {
+    if (!dense && first2 >= 0)
+      slot_block_packed(HIC_SLOT_Z32(zw), first2, o, nf02, (int)(wfirst & 15u), lds_addr(sb));
   }
   __builtin_amdgcn_wave_barrier();
   // ---- 4. copy out, every store instruction 1 KiB contiguous: lengths 16 symbols

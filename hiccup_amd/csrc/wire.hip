@@ -281,8 +281,15 @@ static_assert(sizeof(FillBatch) <= 4096 - 256, "kernel arguments stay under 4 Ki
 
 template <int TABLE, bool SEG>
 __global__ __launch_bounds__(64 * kWPB) void k_slots_fill(FillBatch B) {
-  __shared__ uint32_t s_tile[kWPB][kTileLds];
-  __shared__ __attribute__((aligned(16))) uint2 s_stage[kWPB][64 * kStageU2];
+  // one block, the stages second: slot_pass needs them kSlotStageMin bytes into LDS
+  struct alignas(16) Lds {
+    uint32_t tile[kWPB][kTileLds];
+    uint2 stage[kWPB][64 * kStageU2];
+  };
+  static_assert(offsetof(Lds, stage) >= kSlotStageMin && offsetof(Lds, stage) % 16 == 0, "slot_pass's stage");
+  __shared__ Lds s_lds;
+  auto &s_tile = s_lds.tile;
+  auto &s_stage = s_lds.stage;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int64_t t = (int64_t)blockIdx.x * kWPB + wv;
   if (t >= B.tile0[B.n]) return;  // wave-uniform

@@ -1,6 +1,8 @@
 // Dev micro-benchmark: SIMD cycles per wave64 instruction on gfx950 for the
 // instruction classes of the DCT / colour code (float64 add / fma / mul, int->f64
-// convert, int32 add, 24-bit mad, dot4, f32 fma), at 1, 2 and 4 waves per SIMD.
+// convert, int32 add, 24-bit mad, dot4, f32 fma) and of the slot emission loop
+// (signed 24-bit mad, bit-field extract, 16-bit mad on a high half), at 2 and 4
+// waves per SIMD.
 // Each wave runs 8 independent chains of N instructions (inline asm, so the
 // compiler cannot fold them); SIMD cycles per wave-instruction = wall time x clock
 // / (waves per SIMD x 8 N).  The clock is read in-kernel (s_memtime /
@@ -54,7 +56,12 @@ __global__ __launch_bounds__(256) void k_rate(double *out, unsigned long long *c
   if (K == 20) asm volatile("v_add_u32_e64 %0, %0, %1" : "+v"(v[i]) : "v"(lane));                       \
   if (K == 21) asm volatile("v_sub_u32_sdwa %0, %0, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_1 src1_sel:DWORD" : "+v"(v[i]) : "v"(lane)); \
   if (K == 22) asm volatile("v_cndmask_b32 %0, %0, %1, vcc" : "+v"(v[i]) : "v"(lane));                 \
-  if (K == 23) asm volatile("v_pk_mad_u16 %0, %0, %1, %1" : "+v"(v[i]) : "v"(lane));
+  if (K == 23) asm volatile("v_pk_mad_u16 %0, %0, %1, %1" : "+v"(v[i]) : "v"(lane));                    \
+  if (K == 24) asm volatile("v_mad_i32_i24 %0, %1, -2, %0" : "+v"(v[i]) : "v"(lane));                   \
+  if (K == 25) asm volatile("v_bfe_u32 %0, %0, 3, 1" : "+v"(v[i]));                                     \
+  if (K == 26) asm volatile("v_mad_u32_u16 %0, %1, 16, %0 op_sel:[1,0,0,0]" : "+v"(v[i]) : "v"(lane));  \
+  if (K == 27) asm volatile("v_lshl_or_b32 %0, %1, 4, %0" : "+v"(v[i]) : "v"(lane));                    \
+  if (K == 28) asm volatile("v_and_or_b32 %0, %0, %1, %1" : "+v"(v[i]) : "v"(lane));
     CHAIN8(OPK)
 #undef OPK
   }
@@ -79,14 +86,15 @@ int main() {
   hipEvent_t s, e;
   hipEventCreate(&s);
   hipEventCreate(&e);
-  const char *names[24] = {"v_add_f64", "v_fma_f64", "v_mul_f64", "v_cvt_f64_i32", "v_add_u32", "v_mad_u32_u24",
+  const char *names[29] = {"v_add_f64", "v_fma_f64", "v_mul_f64", "v_cvt_f64_i32", "v_add_u32", "v_mad_u32_u24",
                            "v_dot4_u32_u8", "v_fma_f32", "v_cvt_f32_i32", "v_lshl_add_u64", "v_mov_b64",
                            "v_pk_fma_f32", "v_fmac_f32", "v_sub_u32", "v_lshlrev_b32", "v_mul_u32_u24",
                            "v_perm_b32", "v_pk_add_u16", "v_med3_i32", "v_add3_u32", "v_add_u32_e64",
-                           "v_sub_u32_sdwa", "v_cndmask_b32", "v_pk_mad_u16"};
+                           "v_sub_u32_sdwa", "v_cndmask_b32", "v_pk_mad_u16", "v_mad_i32_i24", "v_bfe_u32",
+                           "v_mad_u32_u16 hi", "v_lshl_or_b32", "v_and_or_b32"};
   for (int wps : {2, 4}) {  // waves per SIMD: workgroups of 4 waves, wps per CU
     const int blocks = cus * wps;
-    for (int k = 0; k < 24; ++k) {
+    for (int k = 0; k < 29; ++k) {
       float best = 1e9;
       unsigned long long h[2] = {0, 0};
       for (int rep = 0; rep < 3; ++rep) {
@@ -94,7 +102,7 @@ int main() {
 #define L(K) \
   if (k == K) hipLaunchKernelGGL(k_rate<K>, dim3(blocks), dim3(256), 0, 0, out, clk, rep);
         L(0) L(1) L(2) L(3) L(4) L(5) L(6) L(7) L(8) L(9) L(10) L(11) L(12) L(13) L(14) L(15) L(16) L(17)
-        L(18) L(19) L(20) L(21) L(22) L(23)
+        L(18) L(19) L(20) L(21) L(22) L(23) L(24) L(25) L(26) L(27) L(28)
 #undef L
         hipEventRecord(e);
         hipEventSynchronize(e);
