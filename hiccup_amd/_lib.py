@@ -84,6 +84,18 @@ class Window(ctypes.Structure):
 STREAM_INDEXED = 0
 STREAM_SLOTS = 1
 
+
+class DecodePlane(ctypes.Structure):
+    """hic_decode_plane (include/hiccup_hip.h): one channel of one image of a batched decode."""
+    _fields_ = [("sym_len", _vp), ("sym_val", _vp), ("d_nsym", _vp), ("dc_diff", _vp), ("d_index", _vp),
+                ("out", _vp), ("d_status", _vp)]
+
+
+class DecodeImage(ctypes.Structure):
+    """hic_decode_image (include/hiccup_hip.h): Y, Cr, Cb of one image."""
+    _fields_ = [("c", DecodePlane * 3)]
+
+
 SIGNATURES = {
     "hic_abi_version": (_int, []),
     "hic_last_error": (_int, [ctypes.c_char_p, _sz]),
@@ -160,6 +172,9 @@ SIGNATURES = {
                                                   ctypes.POINTER(Window), _vp, _i64, _vp, _vp]),
     "hic_rle_decode_idct_rgb_window": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _int, _i64, _i64, ctypes.POINTER(Window),
                                               _vp, _vp, _i64, _vp, _i64, _vp, _vp]),
+    "hic_decode_batch_table_bytes": (_sz, [_int]),
+    "hic_decode_batch_table": (_int, [_int, _int, _i64, _i64, _i64, _i64, _vp, _vp, _sz]),
+    "hic_decode420_batch_u8": (_int, [_vp, _vp, _vp]),
     "hic_event_create": (_int, [_vp]),
     "hic_event_destroy": (_int, [_vp]),
     "hic_event_elapsed_ms": (_int, [_vp, _vp, _vp]),

@@ -547,7 +547,23 @@ def _fast_streams(hic_image):
     the three channels' uint8 / int16 symbols and int32 DC differences on the device,
     Huffman-decoded and range-checked -- or None for anything decode hands to the
     chained calls (its docstring lists them)."""
-    from . import pipeline
+    head = _fast_header(hic_image)
+    if head is None:
+        return None
+    H, W, trees = head
+    p = hic_image.payloads
+    sym = _fast_symbols(H, W, _huffman_streams_device([p[9 + i] for i in range(9)], trees))
+    if sym is None:
+        return None
+    sym_len, sym_val, counts, dc, lim = sym
+    if int(lim.cpu()) < 0:  # one read for the fifteen range checks
+        return None
+    return H, W, sym_len, sym_val, counts, dc
+
+
+def _fast_header(hic_image):
+    """The fast path's checks of a file before its Huffman decode: (H, W, the nine
+    streams' huffman.FlatCodes), or None for a file decode hands to the chained calls."""
     p = hic_image.payloads
     if settings.JPEG_BLOCK_SIZE != 8 or hic_image.hic_type != model.Compression.JPEG or len(p) != 20:
         return None
@@ -564,11 +580,20 @@ def _fast_streams(hic_image):
         # a plane that is not whole 8 x 8 blocks: jpeg_decode's length assertions
         # (codec.py:418) are evaluated on the symbols themselves there
         return None
-    streams = _huffman_streams_device([p[9 + i] for i in range(9)], trees)
+    return H, W, trees
+
+
+def _fast_symbols(H, W, streams):
+    """The fast path's checks of one file's nine Huffman-decoded streams ((tensor,
+    count) in payload order): (sym_len, sym_val, counts, dc, lim) -- the channels'
+    uint8 / int16 symbols and int32 DC differences, the host counts, and a device
+    scalar that is >= 0 when all fifteen range checks hold (the caller reads it, one
+    read for as many files as it likes) -- or None when the counts do not fit."""
+    from . import pipeline
     sym_len, sym_val, dc, counts, lims = {}, {}, {}, [], []
     for c, k in enumerate(pipeline.CHANNELS):
         (D, nd), (V, nv), (L, nl) = streams[c], streams[3 + c], streams[6 + c]
-        nblk = pipeline._nblk(*((H, W) if k == "lum" else (h, w)))
+        nblk = pipeline._nblk(*((H, W) if k == "lum" else (H // 2, W // 2)))
         if nd != nblk or nv != nl or nv < 1:
             return None
         D, V, L = D[:nd], V[:nv], L[:nl]
@@ -577,9 +602,85 @@ def _fast_streams(hic_image):
                  32767 - torch.cumsum(D, 0, dtype=torch.int64).abs().max()]
         sym_len[k], sym_val[k], dc[k] = L.to(torch.uint8), V.to(torch.int16), D.contiguous()
         counts.append(nv)
-    if int(torch.stack(lims).min().cpu()) < 0:  # one read for the fifteen range checks
-        return None
-    return H, W, sym_len, sym_val, counts, dc
+    return sym_len, sym_val, counts, dc, torch.stack(lims).min()
+
+
+def decode_batch(hic_images):
+    """[decode(h) for h in hic_images], byte for byte, with the files the fast path
+    accepts grouped by shape and each group decoded together: its 9 n streams in one
+    batched Huffman decode, its 15 n range checks in one host read, a tile index per
+    image (pipeline.stream_index stays per image), one status read, ONE batched decode
+    of the n images (pipeline.BatchDecoder: two launches) and one copy back.  A file the
+    fast path refuses, and a group the batch refuses, go through decode's per-file
+    path.  If the batched Huffman decode reports an error for any stream the whole
+    call falls back to the per-file path in list order: results and exceptions are
+    then exactly the loop's."""
+    with _gc_paused():
+        return _decode_batch(list(hic_images))
+
+
+def _decode_batch(files):
+    from . import pipeline
+    out = [None] * len(files)
+    groups = {}
+    for i, f in enumerate(files):
+        head = _fast_header(f)
+        if head is not None:
+            groups.setdefault(head[:2], []).append((i, head[2]))
+    for (H, W), members in groups.items():
+        for at in range(0, len(members), pipeline.DECODE_BATCH_MAX):
+            part = members[at:at + pipeline.DECODE_BATCH_MAX]
+            if not pipeline.batch_decode_eligible(len(part), H, W):
+                continue
+            try:
+                got = _decode_group(H, W, [(i, files[i], trees) for i, trees in part])
+            except _HuffmanBatchError:
+                return [_decode(f) for f in files]
+            for i, a in got:
+                out[i] = a
+    for i, f in enumerate(files):  # everything the groups left, in list order
+        if out[i] is None:
+            out[i] = _decode(f)
+    return out
+
+
+class _HuffmanBatchError(Exception):
+    """The batched Huffman decode of a group reported an error for some stream."""
+
+
+def _decode_group(H, W, members):
+    """[(list position, RGB array)] of the (position, file, trees) of one shape that
+    decode together; the ones missing from the result take the per-file path."""
+    from . import pipeline
+    payloads, trees = [], []
+    for _, f, t in members:
+        payloads += [f.payloads[9 + j] for j in range(9)]
+        trees += t
+    try:
+        streams = _huffman_streams_device(payloads, trees)
+    except Exception as e:  # noqa: BLE001 -- whichever stream failed: the loop decides what is raised
+        raise _HuffmanBatchError() from e
+    syms = [(i, _fast_symbols(H, W, streams[9 * m:9 * m + 9])) for m, (i, _, _) in enumerate(members)]
+    syms = [(i, s) for i, s in syms if s is not None]
+    if not syms:
+        return []
+    lims = torch.stack([s[4] for _, s in syms]).cpu().tolist()  # one read for the group's range checks
+    syms = [(i, s) for (i, s), lim in zip(syms, lims) if lim >= 0]
+    if not syms:
+        return []
+    # a tile index per image from its bare streams; the statuses (what the un-indexed
+    # decode would report) in one read: Decoder.check_status's test for every image
+    indexed = [(i, s, pipeline.stream_index(s[0], s[1], s[2], s[3], H, W)) for i, s in syms]
+    want = [pipeline._nblk(H, W) * 63] + [pipeline._nblk(H // 2, W // 2) * 63] * 2
+    status = torch.stack([st for _, _, (_, st) in indexed]).cpu().tolist()
+    good = [(i, s, ix) for (i, s, (ix, _)), st in zip(indexed, status) if st == want]
+    if not good:
+        return []
+    counts = device.to_device(np.asarray([s[2] for _, s, _ in good], np.int64))
+    dec = pipeline.BatchDecoder(len(good), H, W)
+    rgb = dec.decode([(s[0], s[1], counts[m], s[3], ix) for m, (_, s, ix) in enumerate(good)])
+    host = device.to_host(rgb)  # one copy back
+    return [(i, host[m]) for m, (i, _, _) in enumerate(good)]
 
 
 class OpenImage:

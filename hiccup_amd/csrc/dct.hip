@@ -23,11 +23,15 @@
 //    lane recomputes rint(b / D) with the IEEE-correct divide, which is what
 //    numpy does.  The guard is > 10^3 x the reciprocal's error bound.
 #include <stdlib.h>
+#include <string.h>
 
+#include <algorithm>
 #include <type_traits>
+#include <vector>
 
 #include "color_core.h"
 #include "dct_core.h"
+#include "decode_batch.h"
 #include "rle_core.h"
 
 namespace hic {
@@ -332,11 +336,13 @@ struct WinGeo {
 };
 template <bool WIN>
 using WinArg = std::conditional_t<WIN, WinGeo, NoWin>;
-template <bool WIN = false>
+// PITCH (the batched decode, whole planes): the chroma planes' rows are cpitch bytes
+// apart instead of packed.
+template <bool WIN = false, bool PITCH = false>
 __device__ __forceinline__ void colour_block(const uint32_t (&px)[16], int bi, int bj, int nbx, int nby, int lane,
                                              bool live, const uint8_t *__restrict__ cr, const uint8_t *__restrict__ cb,
                                              uint8_t *__restrict__ rgb, int64_t rgb_stride,
-                                             const WinArg<WIN> &g = WinArg<WIN>{}, int wbi = 0) {
+                                             const WinArg<WIN> &g = WinArg<WIN>{}, int wbi = 0, int64_t cpitch = 0) {
   const int w = 4 * nbx, h = 4 * nby;
   // The packed pixels are opaque: otherwise the compiler forwards each truncated
   // pixel past its packing to the byte extracts below, and 64 live values instead
@@ -378,7 +384,9 @@ __device__ __forceinline__ void colour_block(const uint32_t (&px)[16], int bi, i
     for (int r = 0; r < 6; ++r) {
       int s = 4 * bi - 1 + r;
       s = s < 0 ? 1 : (s >= h ? h - 1 : s);
-      const int64_t ro = (int64_t)s * w;
+      int64_t ro;
+      if constexpr (PITCH) ro = (int64_t)s * cpitch;
+      else ro = (int64_t)s * w;
       dcr[r] = *reinterpret_cast<const uint32_t *>(cr + ro + 4 * bj);
       dcb[r] = *reinterpret_cast<const uint32_t *>(cb + ro + 4 * bj);
       ecr[r] = *reinterpret_cast<const uint32_t *>(cr + ro + ce);
@@ -618,6 +626,115 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HIC_DEC_WPE
     idct_block_store<TABLE, true>(qv, H, W, bi * 8 - wg.oy, bj * 8 - wg.ox, out, ostride);
   } else {
     idct_block_store<TABLE, FAST>(qv, H, W, bi * 8, bj * 8, out, ostride);
+  }
+}
+
+// The batched form (hic_decode420_batch_u8, decode_batch.h): per wave exactly what
+// k_rld_idct_indexed<TABLE, true, RGB, SLOTS> does for one tile, the plane's pointers
+// read from the batch's table in device memory.  One wave per tile, per-wave LDS and
+// only wave barriers, so the four waves of a workgroup may belong to different planes
+// and to different images.  With g = blockIdx.x * 4 + wave and T = a.tiles waves per
+// image (RGB: Y's tiles; else Cr's tiles, then Cb's): image g / T, plane (g % T) /
+// ntiles, tile (g % T) % ntiles; a wave with g >= n * T returns.  All of it is
+// wave-uniform and kept in SGPRs, so the table entry is read by scalar loads.  The
+// body is a copy of the one-image kernel's (sharing it through a function changes the
+// existing kernels' register allocation, profiles/r14/decode_batch/isa_identity.txt).
+// The chroma planes' rows are a.cstride bytes apart (>= W / 2, a multiple of 4): the
+// plane form stores dwords, the RGB form loads dwords.
+struct DecBatchArgs {
+  const DecBatchEntry *tab;
+  uint32_t total, tiles;  // n * T, T
+  int H, W, nbx;          // of the launch's planes
+  int ntiles;             // of one plane
+  int64_t nblk;
+  int64_t ostride;        // RGB form: of the pixels; plane form: of the chroma planes
+  int64_t cstride;        // RGB form: of the chroma planes it reads
+};
+template <int TABLE, bool RGB, bool SLOTS>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HIC_DEC_WPE))) void k_rld_idct_batch(DecBatchArgs a) {
+  static_assert(!RGB || TABLE == 0, "the RGB form decodes luma planes");
+  __shared__ uint2 s_tile[4][64 * kRowI16 / 4];
+  const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint32_t g = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (uint32_t)wv);
+  if (g >= a.total) return;
+  const uint32_t img = g / a.tiles, r = g - img * a.tiles;
+  const bool second = !RGB && r >= (uint32_t)a.ntiles;  // Cb's tiles follow Cr's
+  const int64_t t = second ? r - (uint32_t)a.ntiles : r;
+  // the entry through a constant-address-space pointer: a uniform address, scalar loads
+  typedef const __attribute__((address_space(4))) DecBatchEntry centry;
+  centry *ent = (centry *)(uintptr_t)(a.tab + img);
+  const int ch = RGB ? 0 : (second ? 2 : 1);
+  const uint8_t *__restrict__ sym_len = ent->c[ch].sym_len;
+  const int16_t *__restrict__ sym_val = ent->c[ch].sym_val;
+  const int64_t *__restrict__ d_nsym = ent->c[ch].d_nsym;
+  const int32_t *__restrict__ dc_diff = ent->c[ch].dc_diff;
+  const int64_t *__restrict__ index = static_cast<const int64_t *>(ent->c[ch].index);
+  uint8_t *__restrict__ out = ent->c[ch].out;
+  int64_t *__restrict__ d_status = ent->c[ch].d_status;
+  const int nbx = a.nbx, rsh = RGB ? 0 : 1;
+  const int64_t nblk = a.nblk, ntiles = a.ntiles;
+  uint2 *tile = s_tile[wv];
+  int16_t *win = reinterpret_cast<int16_t *>(tile);
+  const int64_t nsym_raw = *d_nsym, nsym = nsym_raw > 0 ? nsym_raw : 0;
+  const int nvb = (int)(nblk - t * 64 < 64 ? nblk - t * 64 : 64);
+  const int64_t blk = t * 64 + lane;
+  const int d = lane < nvb ? dc_diff[blk] : 0;
+  __builtin_amdgcn_s_setprio(1);
+  SlotTileIx six;
+  if constexpr (SLOTS) six = slot_tile_ix(reinterpret_cast<const int32_t *>(index), t, rsh, nblk);
+  for (int i = lane; i < 64 * kRowI16 / 4; i += 64) tile[i] = make_uint2(0, 0);
+  __builtin_amdgcn_wave_barrier();
+  const int64_t tb0 = t * 64 * 63;
+  const int span = nvb * 63;
+  int P, pdc;
+  if constexpr (SLOTS) {
+    P = slots_gather_tile<kRowI16>(sym_len, sym_val, six, t, rsh, span, win, lane * kRowI16 + 64, lane);
+    pdc = six.r[0].z;
+  } else {
+    const int64_t o0 = index[3 * t] < nsym ? index[3 * t] : nsym;
+    const int64_t o1 = t + 1 < ntiles ? (index[3 * (t + 1)] < nsym ? index[3 * (t + 1)] : nsym) : nsym;
+    P = gather_tile<kRowI16, HIC_DEC_G, HIC_DEC_PF>(sym_len, sym_val, o0, o1, nsym, (int)(index[3 * t + 1] + 1 - tb0),
+                                                    span, win, lane * kRowI16 + 64, lane);
+    pdc = (int)index[3 * t + 2];
+  }
+  win[lane * kRowI16] = (int16_t)(pdc + wave_incl_sum_i32(d));
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_s_setprio(0);
+  if (t == ntiles - 1 && lane == 0) {
+    const int64_t total = tb0 + (int64_t)P, n_ac = nblk * 63;
+    const bool eob = SLOTS || (nsym > 0 && sym_len[nsym - 1] == 0 && sym_val[nsym - 1] == 0);
+    *d_status = nsym_raw < 1 ? -1 : ((eob && (SLOTS || total <= n_ac)) ? n_ac : total);
+  }
+  if (!RGB && lane >= nvb) return;
+  int qv[64];  // raster [u][v]
+  {
+    const uint2 *row = tile + (lane < nvb ? lane : nvb - 1) * (kRowI16 / 4);
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+      const uint2 x = row[k];
+      qv[ZZ[4 * k]] = (int)(int16_t)(x.x & 0xFFFFu);
+      qv[ZZ[4 * k + 1]] = (int)(int16_t)(x.x >> 16);
+      qv[ZZ[4 * k + 2]] = (int)(int16_t)(x.y & 0xFFFFu);
+      qv[ZZ[4 * k + 3]] = (int)(int16_t)(x.y >> 16);
+    }
+  }
+  const int64_t blk_c = lane < nvb ? blk : t * 64 + nvb - 1;  // RGB: the dead lanes redo the last block
+  const int bi = (int)(blk_c / nbx), bj = (int)(blk_c - (int64_t)bi * nbx);
+  uint32_t px[16];
+  idct_block_px<TABLE>(qv, px);
+  if constexpr (RGB) {
+    const uint8_t *__restrict__ cr = ent->c[1].out;
+    const uint8_t *__restrict__ cb = ent->c[2].out;
+    colour_block<false, true>(px, bi, bj, nbx, a.H / 8, lane, lane < nvb, cr, cb, out, a.ostride, NoWin{}, 0, a.cstride);
+  } else {
+    // (rows 4 bytes aligned: the pitch is a multiple of 4, not of 8)
+    uint8_t *o = out + (int64_t)bi * 8 * a.ostride + bj * 8;
+#pragma unroll
+    for (int rr = 0; rr < 8; ++rr) {
+      uint32_t *o32 = reinterpret_cast<uint32_t *>(o + rr * a.ostride);
+      o32[0] = px[2 * rr];
+      o32[1] = px[2 * rr + 1];
+    }
   }
 }
 
@@ -1392,6 +1509,129 @@ extern "C" int hic_rle_decode_idct_rgb_window(int kind, const uint8_t *sym_len, 
   d.rgb = true, d.cr = cr, d.cb = cb;
   d.slots = kind == HIC_STREAM_SLOTS, d.records_per_tile = records_per_tile;
   return launch_rld_idct_window(d, kind, win, chroma_stride, stream);
+}
+
+// ---- batched decode: n images of one shape in two launches (decode_batch.h, DESIGN.md
+// section 5, "Batched decode").  The header of (kind, n, H, W, strides); nullptr =
+// good, else what is wrong with them.
+static const char *dec_batch_header(int kind, int n, int64_t H, int64_t W, int64_t rgb_stride, int64_t chroma_stride,
+                                    DecBatchHeader &h) {
+  if (kind != HIC_STREAM_INDEXED && kind != HIC_STREAM_SLOTS) return "stream kind";
+  if (n < 1 || n > HIC_DECODE_BATCH_MAX) return "1 <= n <= HIC_DECODE_BATCH_MAX images";
+  if (H < 16 || W < 16 || H % 16 || W % 16 || H >= (1 << 20) || W >= (1 << 20))
+    return "image shape (H, W multiples of 16, at least 16)";
+  if ((H / 8) * (W / 8) * 63 >= ((int64_t)1 << 31)) return "plane too large (AC stream >= 2^31)";
+  if (!dims_ok(H, W)) return "image shape (too many blocks)";
+  if (rgb_stride < 3 * W || rgb_stride % 8) return "rgb_stride (>= 3 W, a multiple of 8)";
+  if (chroma_stride < W / 2 || chroma_stride % 4) return "chroma_stride (>= W / 2, a multiple of 4)";
+  h = DecBatchHeader{};
+  h.magic = kDecBatchMagic;
+  h.kind = kind, h.n = n, h.H = H, h.W = W, h.rgb_stride = rgb_stride, h.chroma_stride = chroma_stride;
+  h.nblk_y = (H / 8) * (W / 8), h.nblk_c = (H / 16) * (W / 16);
+  if (kind == HIC_STREAM_SLOTS && (h.nblk_y % 64 || h.nblk_c % 32))
+    return "the planes' blocks must form whole records (Y: 64, chroma: 32)";
+  const int64_t ty = (h.nblk_y + 63) / 64, tc = 2 * ((h.nblk_c + 63) / 64);
+  const int64_t gy = (n * ty + 3) / 4, gc = (n * tc + 3) / 4;
+  // (the kernel counts waves in 32 bits, unsigned)
+  if (gy > INT32_MAX || gc > INT32_MAX || 4 * gy > UINT32_MAX || 4 * gc > UINT32_MAX)
+    return "grid above INT32_MAX workgroups";
+  h.tiles_y = (int32_t)ty, h.tiles_c = (int32_t)tc, h.grid_y = (int32_t)gy, h.grid_c = (int32_t)gc;
+  return nullptr;
+}
+
+extern "C" size_t hic_decode_batch_table_bytes(int n) {
+  if (n < 1 || n > HIC_DECODE_BATCH_MAX) return 0;
+  return sizeof(DecBatchHeader) + (size_t)n * sizeof(DecBatchEntry);
+}
+
+extern "C" int hic_decode_batch_table(int kind, int n, int64_t H, int64_t W, int64_t rgb_stride, int64_t chroma_stride,
+                                      const hic_decode_image *images, void *h_table, size_t table_bytes) {
+  DecBatchHeader h;
+  if (const char *e = dec_batch_header(kind, n, H, W, rgb_stride, chroma_stride, h)) return arg_error(e);
+  if (!images || !h_table) return arg_error("null pointer");
+  if (table_bytes < hic_decode_batch_table_bytes(n))
+    return arg_error("table of %lld bytes, %lld needed", (long long)table_bytes,
+                     (long long)hic_decode_batch_table_bytes(n));
+  // every image checked before a byte is written
+  const bool slots = kind == HIC_STREAM_SLOTS;
+  for (int i = 0; i < n; ++i)
+    for (int k = 0; k < 3; ++k) {
+      const hic_decode_plane &p = images[i].c[k];
+      if (!p.sym_len || !p.sym_val || !p.d_nsym || !p.dc_diff || !p.d_index || !p.out || !p.d_status)
+        return arg_error("image %d channel %d: null pointer", i, k);
+      // the gathers read the symbols as uint4s
+      if (!aligned(p.sym_len, 16) || !aligned(p.sym_val, 16))
+        return arg_error("image %d channel %d: %s arrays must be 16-byte aligned", i, k, slots ? "slot" : "symbol");
+      // 8-byte pixel stores, dword chroma stores and loads
+      if (!aligned(p.out, 8)) return arg_error("image %d channel %d: out must be 8-byte aligned", i, k);
+      if (!aligned(p.d_nsym, 8) || !aligned(p.d_status, 8) || !aligned(p.dc_diff, 4) ||
+          !aligned(p.d_index, slots ? 4 : 8))
+        return arg_error("image %d channel %d: count / status / DC / index alignment", i, k);
+    }
+  // no two outputs of the batch may overlap (pixels, chroma planes, status words): sorted
+  // by address, a range must end before the next one starts
+  {
+    struct Range {
+      uintptr_t at, bytes;
+      int image, chan, status;
+    };
+    std::vector<Range> r;
+    r.reserve((size_t)6 * n);
+    for (int i = 0; i < n; ++i)
+      for (int k = 0; k < 3; ++k) {
+        const hic_decode_plane &p = images[i].c[k];
+        const int64_t bytes = k == 0 ? (H - 1) * rgb_stride + 3 * W : (H / 2 - 1) * chroma_stride + W / 2;
+        r.push_back(Range{reinterpret_cast<uintptr_t>(p.out), (uintptr_t)bytes, i, k, 0});
+        r.push_back(Range{reinterpret_cast<uintptr_t>(p.d_status), 8, i, k, 1});
+      }
+    std::sort(r.begin(), r.end(), [](const Range &x, const Range &y) { return x.at < y.at; });
+    const char *what[2] = {"output", "status word"};
+    for (size_t i = 0; i + 1 < r.size(); ++i)
+      if (r[i].at + r[i].bytes > r[i + 1].at)
+        return arg_error("image %d channel %d: its %s overlaps the %s of image %d channel %d", r[i + 1].image,
+                         r[i + 1].chan, what[r[i + 1].status], what[r[i].status], r[i].image, r[i].chan);
+  }
+  memcpy(h_table, &h, sizeof h);
+  DecBatchEntry *ent = reinterpret_cast<DecBatchEntry *>(static_cast<char *>(h_table) + sizeof h);
+  for (int i = 0; i < n; ++i) {
+    DecBatchEntry e{};
+    for (int k = 0; k < 3; ++k) {
+      const hic_decode_plane &p = images[i].c[k];
+      e.c[k] = DecBatchPlane{p.sym_len, p.sym_val, p.d_nsym, p.dc_diff, p.d_index, p.out, p.d_status};
+    }
+    memcpy(ent + i, &e, sizeof e);
+  }
+  return HIC_OK;
+}
+
+extern "C" int hic_decode420_batch_u8(const void *h_table, const void *d_table, void *stream) {
+  if (!h_table || !d_table) return arg_error("null pointer");
+  if (!aligned(d_table, 16)) return arg_error("d_table must be 16-byte aligned");
+  DecBatchHeader h;
+  memcpy(&h, h_table, sizeof h);
+  if (h.magic != kDecBatchMagic) return arg_error("not a decode batch table (magic)");
+  DecBatchHeader want;
+  if (const char *e = dec_batch_header(h.kind, h.n, h.H, h.W, h.rgb_stride, h.chroma_stride, want)) return arg_error(e);
+  if (memcmp(&want, &h, sizeof want)) return arg_error("damaged decode batch table header");
+  DecBatchArgs a{};
+  a.tab = reinterpret_cast<const DecBatchEntry *>(static_cast<const char *>(d_table) + sizeof h);
+  const bool slots = h.kind == HIC_STREAM_SLOTS;
+  hipStream_t s = as_stream(stream);
+  const dim3 block(256);
+  // every image's Cr and Cb planes ...
+  a.total = (uint32_t)h.n * (uint32_t)h.tiles_c, a.tiles = (uint32_t)h.tiles_c;
+  a.H = (int)(h.H / 2), a.W = (int)(h.W / 2), a.nbx = (int)(h.W / 16), a.ntiles = h.tiles_c / 2, a.nblk = h.nblk_c;
+  a.ostride = h.chroma_stride, a.cstride = 0;
+  if (slots) hipLaunchKernelGGL((k_rld_idct_batch<1, false, true>), dim3((unsigned)h.grid_c), block, 0, s, a);
+  else hipLaunchKernelGGL((k_rld_idct_batch<1, false, false>), dim3((unsigned)h.grid_c), block, 0, s, a);
+  if (int e = check_launch("k_rld_idct_batch<chroma>")) return e;
+  // ... then every image's Y tiles straight to RGB, through its own chroma planes
+  a.total = (uint32_t)h.n * (uint32_t)h.tiles_y, a.tiles = (uint32_t)h.tiles_y;
+  a.H = (int)h.H, a.W = (int)h.W, a.nbx = (int)(h.W / 8), a.ntiles = h.tiles_y, a.nblk = h.nblk_y;
+  a.ostride = h.rgb_stride, a.cstride = h.chroma_stride;
+  if (slots) hipLaunchKernelGGL((k_rld_idct_batch<0, true, true>), dim3((unsigned)h.grid_y), block, 0, s, a);
+  else hipLaunchKernelGGL((k_rld_idct_batch<0, true, false>), dim3((unsigned)h.grid_y), block, 0, s, a);
+  return check_launch("k_rld_idct_batch<rgb>");
 }
 
 extern "C" int hic_dct2_f64(const double *in, int64_t nblk, double *out, void *stream) {

@@ -680,6 +680,148 @@ class Decoder:
                 raise ValueError("channel %s: stream covers %d AC positions, expected %d" % (k, st[i], want))
 
 
+# ------------------------------------------------------------------ batched decode
+DECODE_BATCH_MAX = 4096  # HIC_DECODE_BATCH_MAX (include/hiccup_hip.h)
+
+
+def batch_decode_eligible(n, H, W, slots=False):
+    """Whether BatchDecoder takes n images of H x W (hic_decode_batch_table's limits): 1
+    <= n <= DECODE_BATCH_MAX, H and W multiples of 16 (whole 8 x 8 blocks in all three
+    planes) below 2^20, each plane's AC stream below 2^31 positions; slots=True: the
+    planes also whole slot-layout records (Y: 64 blocks, chroma: 32)."""
+    if not (1 <= n <= DECODE_BATCH_MAX and 16 <= H < 2**20 and 16 <= W < 2**20 and H % 16 == 0 and W % 16 == 0):
+        return False
+    ny, nc = _nblk(H, W), _nblk(H // 2, W // 2)
+    if ny >= 2**31 // 256 or ny * 63 >= 2**31 or (slots and (ny % 64 or nc % 32)):
+        return False
+    ty, tc = -(-ny // 64), 2 * -(-nc // 64)
+    return 4 * -(-n * ty // 4) <= 2**32 - 1 and 4 * -(-n * tc // 4) <= 2**32 - 1
+
+
+class BatchDecoder:
+    """Decoder.decode(index=...) of n images of one shape in TWO launches
+    (hic_decode420_batch_u8) instead of two per image: every image's Cr and Cb tiles,
+    then every image's Y tiles straight to RGB.  A 512 x 512 image is 8 + 16
+    workgroups of the tile decoder, and a run of such launches is bound by launch
+    latency.  Per image the results are bit for bit those of Decoder(H, W).decode:
+    rgb (n, H, W, 3), cr / cb (n, H/2, W/2), status (n, 3)."""
+
+    def __init__(self, n, H, W):
+        if not batch_decode_eligible(n, H, W):
+            raise ValueError("a decode batch needs 1 <= n <= %d images with H and W multiples of 16"
+                             % DECODE_BATCH_MAX)
+        device.require_gpu()
+        self.n, self.H, self.W = n, H, W
+        self.rgb = device.empty((n, H, W, 3), torch.uint8)
+        self.cr = device.empty((n, H // 2, W // 2), torch.uint8)
+        self.cb = device.empty((n, H // 2, W // 2), torch.uint8)
+        self.status = device.zeros((n, 3), torch.int64)
+        self._key = self._h_table = self._d_table = self._objs = None
+
+    def _source(self, i, src):
+        """Source i as (kind, the 15 stream addresses: per channel symbols / slots, values,
+        count, DC differences, index)."""
+        nblk = (_nblk(self.H, self.W), _nblk(self.H // 2, self.W // 2), _nblk(self.H // 2, self.W // 2))
+        if isinstance(src, Encoder):
+            if (src.H, src.W) != (self.H, self.W) or src.rows != (0, src.H):
+                raise ValueError("source %d: a whole %d x %d image is needed" % (i, self.H, self.W))
+            if src.index is None:
+                raise ValueError("source %d: the encoder has no index (a slot encoder or index=True)" % i)
+            src = (src.sym_len, src.sym_val, src.counts, src.dc, src.index)
+        if not (isinstance(src, (tuple, list)) and len(src) == 5):
+            raise ValueError("source %d: an Encoder or (sym_len, sym_val, counts, dc, index)" % i)
+        sym_len, sym_val, counts, dc, index = src
+        slots = isinstance(index, SlotIndex)
+        if slots:
+            sym_len, sym_val = index.slot_len, index.slot_val
+            if any(index.rpt[k] != SLOT_RPT[k] for k in CHANNELS):
+                raise ValueError("source %d: not the slot layout's records per tile" % i)
+        if not (isinstance(counts, torch.Tensor) and counts.is_cuda and counts.dtype == torch.int64
+                and counts.numel() == 3 and counts.is_contiguous()):
+            raise ValueError("source %d: counts must be a (3,) int64 device tensor" % i)
+        addr = []
+        for c, k in enumerate(CHANNELS):
+            if dc[k].numel() != nblk[c]:
+                raise ValueError("source %d channel %s: %d DC differences, a %d x %d image has %d blocks"
+                                 % (i, k, dc[k].numel(), self.H, self.W, nblk[c]))
+            want = 4 * (nblk[c] * SLOT_RPT[k] // 64) if slots else 3 * -(-nblk[c] // 64)
+            if index[k].numel() != want or (slots and sym_len[k].numel() != nblk[c] * 63):
+                raise ValueError("source %d channel %s: the index is not a %d x %d image's" % (i, k, self.H, self.W))
+            addr += [sym_len[k].data_ptr(), sym_val[k].data_ptr(), counts.data_ptr() + 8 * c, dc[k].data_ptr(),
+                     index[k].data_ptr()]
+        return slots, addr
+
+    def _table(self, sources, stream):
+        # The same BatchEncoder, or the same Encoder objects, as the previous call: an
+        # Encoder's buffers are allocated once, so the addresses are the same too, and
+        # the 15 n data_ptr() reads (several us per image on the host, more than the
+        # batch's GPU time for small images) are skipped.  Tuples are always compared
+        # by address.
+        whole = isinstance(sources, BatchEncoder)
+        objs = (sources,) if whole else tuple(sources)
+        if self._objs is not None and self._objs[0] == whole and len(objs) == len(self._objs[1]) and all(
+                a is b for a, b in zip(objs, self._objs[1])):
+            return
+        self._objs = None
+        sources = objs[0].encoders if whole else list(objs)
+        if len(sources) != self.n:
+            raise ValueError("%d sources for a batch of %d" % (len(sources), self.n))
+        kinds, addrs = zip(*(self._source(i, s) for i, s in enumerate(sources)))
+        if len(set(kinds)) != 1:
+            raise ValueError("the sources of a batch must be of one kind (slot layout or indexed streams)")
+        key = (kinds[0], addrs)
+        remember = (whole, objs) if all(isinstance(x, Encoder) for x in sources) else None
+        if key == self._key:
+            self._objs = remember
+            return
+        n, H, W = self.n, self.H, self.W
+        if kinds[0] and not batch_decode_eligible(n, H, W, slots=True):
+            raise ValueError("slot-layout sources need planes of whole records")
+        images = (_lib.DecodeImage * n)()
+        outs = (self.rgb, self.cr, self.cb)
+        for i, a in enumerate(addrs):
+            for c in range(3):
+                images[i].c[c] = _lib.DecodePlane(*a[5 * c:5 * c + 5], outs[c][i].data_ptr(),
+                                                  self.status.data_ptr() + 8 * (3 * i + c))
+        nbytes = _lib.load().hic_decode_batch_table_bytes(n)
+        h_table = ctypes.create_string_buffer(nbytes)
+        _lib.call("hic_decode_batch_table", _lib.STREAM_SLOTS if kinds[0] else _lib.STREAM_INDEXED, n, H, W, 3 * W,
+                  W // 2, images, h_table, nbytes)
+        # uploaded on the decode's stream: the launches that read it follow the copy
+        with device.on_stream(stream):
+            d_table = device.to_device(np.frombuffer(h_table, np.uint8, nbytes))
+        self._key, self._h_table, self._d_table, self._objs = key, h_table, d_table, remember
+
+    def decode(self, sources, stream=None):
+        """sources: a BatchEncoder, or a sequence of n Encoders (slot encoders or
+        index=True encoders) or of n tuples (sym_len, sym_val, counts, dc, index) as
+        Decoder.decode(index=...) takes them, counts the (3,) device tensor; all of one
+        kind.  The table is rebuilt and uploaded only when the sources' addresses differ
+        from the previous call's (the same BatchEncoder or Encoder objects as in the
+        previous call have the same addresses: their buffers are allocated once);
+        otherwise nothing crosses to or from the host.  Returns self.rgb."""
+        self._table(sources, stream)
+        if stream is not None:
+            self._d_table.record_stream(stream)
+        _lib.call("hic_decode420_batch_u8", self._h_table, device.ptr(self._d_table), device.stream_ptr(stream))
+        return self.rgb
+
+    def expected_status(self):
+        c = _nblk(self.H // 2, self.W // 2) * 63
+        return [_nblk(self.H, self.W) * 63, c, c]
+
+    def check_status(self):
+        """Raise unless every channel of every image decoded to exactly its blocks' AC
+        positions (Decoder.check_status for the batch; one read, syncs)."""
+        st = self.status.cpu().tolist()
+        want = self.expected_status()
+        for i, row in enumerate(st):
+            for c, k in enumerate(CHANNELS):
+                if row[c] != want[c]:
+                    raise ValueError("image %d channel %s: stream covers %d AC positions, expected %d"
+                                     % (i, k, row[c], want[c]))
+
+
 # ------------------------------------------------------------------ region decode
 class WindowPlan(collections.namedtuple("WindowPlan", "Y0 X0 Y1 X1 cy0 cx0 ch cw")):
     """hic_window (include/hiccup_hip.h): the 16-pixel-aligned covering window

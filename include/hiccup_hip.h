@@ -603,6 +603,46 @@ int hic_rle_decode_idct_rgb_window(int kind, const uint8_t *sym_len, const int16
                                    int64_t W, const hic_window *win, const uint8_t *cr, const uint8_t *cb,
                                    int64_t chroma_stride, uint8_t *rgb, int64_t rgb_stride, int64_t *d_status,
                                    void *stream);
+/* Batched decode: n images of one shape (H, W multiples of 16), each decoded as
+ *  hic_rle_decode_idct_u8_{indexed,slots}_pair + hic_rle_decode_idct_rgb_{indexed,slots}
+ *  decode it, by TWO launches for the whole batch: every image's Cr and Cb tiles, then
+ *  every image's Y tiles straight to RGB (each image reads its own Cr / Cb planes).
+ *  The per-image pointers live in a table in device memory.  The library allocates
+ *  nothing: hic_decode_batch_table fills a host blob of hic_decode_batch_table_bytes(n)
+ *  bytes (0 unless 1 <= n <= HIC_DECODE_BATCH_MAX), the caller uploads it once
+ *  (16-byte aligned) and passes both copies to hic_decode420_batch_u8.
+ *  hic_decode_batch_table: kind is HIC_STREAM_*, the same for every image (slots: rsh 0
+ *    for Y and 1 for chroma, i.e. 1 and 2 records per tile); images[i].c[0..2] = image
+ *    i's Y, Cr, Cb.  Image i's pixels are rows of rgb_stride bytes from c[0].out
+ *    (rgb_stride >= 3 W, % 8 == 0), its chroma planes rows of chroma_stride bytes from
+ *    c[1].out / c[2].out (chroma_stride >= W / 2, % 4 == 0).  Every image is checked
+ *    before a byte is written; HIC_ERR_ARG, the message naming the image and channel,
+ *    for a null pointer, symbol / slot arrays not 16-byte aligned, an output not 8-byte
+ *    aligned, a bad stride or shape, a plane whose AC stream reaches 2^31, slot planes
+ *    that are not whole records (Y: 64 blocks, chroma: 32), a short table_bytes, a grid
+ *    above INT32_MAX, and any two outputs (pixels, chroma planes, status words) of the
+ *    batch that overlap.
+ *  hic_decode420_batch_u8: the two launches on one stream.  *d_status of every (image,
+ *    channel) as the one-image entry points write it: nblk * 63 for a whole stream, the
+ *    positions covered for a short one, -1 when *d_nsym < 1.  A foreign or damaged
+ *    blob is HIC_ERR_ARG before any launch. */
+typedef struct {
+  const uint8_t *sym_len; /* or the slots */
+  const int16_t *sym_val;
+  const int64_t *d_nsym;
+  const int32_t *dc_diff;
+  const void *d_index;    /* int64 tile index, or the close's int32 record index */
+  uint8_t *out;           /* Y: the image's RGB pixels; Cr / Cb: its H/2 x W/2 plane */
+  int64_t *d_status;
+} hic_decode_plane;
+typedef struct {
+  hic_decode_plane c[3]; /* Y, Cr, Cb */
+} hic_decode_image;
+#define HIC_DECODE_BATCH_MAX 4096
+size_t hic_decode_batch_table_bytes(int n);
+int hic_decode_batch_table(int kind, int n, int64_t H, int64_t W, int64_t rgb_stride, int64_t chroma_stride,
+                           const hic_decode_image *images, void *h_table, size_t table_bytes);
+int hic_decode420_batch_u8(const void *h_table, const void *d_table, void *stream);
 /* One tile shard's slice of the channel stream (the sharded decode of
  * codec.jpeg_decode, codec.py:397-425): d_stitch is the shard's device record from
  * hic_rle_stitch {carry zeros, closes the stream, has previous DC, previous DC}.
