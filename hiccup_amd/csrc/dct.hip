@@ -483,6 +483,91 @@ struct DecPlane {
   uint8_t *out;
   int64_t *d_status;
 };
+// One wave decodes tile t of plane p into the wave's LDS rows `tile` and stores its
+// blocks: the body of k_rld_idct_indexed and of the batched k_rld_idct_batch, which
+// differ in how a wave finds p and t.  TABLE, FAST, RGB, SLOTS, WIN as the kernels'.
+// RSH >= 0 (the batch: Y 0, chroma 1): the records per tile are the compile-time
+// 1 << RSH, rsh_arg is not read and the slot gather has no branch on it.  PITCH (the
+// batch): the chroma planes' rows are `ostride` (plane form, stored as dwords: a
+// multiple of 4, not of 8) or `cpitch` (RGB form, read) bytes apart.
+template <int TABLE, bool FAST, bool RGB, bool SLOTS, bool WIN, bool PITCH = false, int RSH = -1>
+__device__ __forceinline__ void decode_tile(const DecPlane &p, int64_t t, uint2 *tile, int lane, int H, int W, int nbx,
+                                            int64_t nblk, int64_t ostride, const uint8_t *__restrict__ cr,
+                                            const uint8_t *__restrict__ cb, int rsh_arg, const WinArg<WIN> &wg,
+                                            int wbi, bool wfirst, int64_t cpitch = 0) {
+  static_assert(!PITCH || (FAST && !WIN), "the pitched form holds whole planes of whole blocks");
+  const int rsh = RSH >= 0 ? RSH : rsh_arg;
+  const int64_t ntiles = (nblk + 63) / 64;
+  int16_t *win = reinterpret_cast<int16_t *>(tile);
+  const int64_t nsym_raw = *p.d_nsym, nsym = nsym_raw > 0 ? nsym_raw : 0;
+  if constexpr (WIN) {
+    if (wfirst && lane == 0) *p.d_status = nsym_raw < 1 ? -1 : wg.n_ac;
+    if (nsym_raw < 1) return;  // a failed encode's count: nothing is decoded or stored
+  }
+  const int nvb = (int)(nblk - t * 64 < 64 ? nblk - t * 64 : 64);
+  const int64_t blk = t * 64 + lane;
+  // loads that depend on nothing else go out before the zero-fill: this lane's DC
+  // difference and (slot layout) the tile's record index
+  const int d = lane < nvb ? p.dc_diff[blk] : 0;
+  // the gather (index, symbol loads, LDS scatter) at issue priority 1 over the
+  // SIMD's waves in their IDCT / colour: 16K decode 0.713-0.766 vs 0.749-0.807 ms,
+  // faster in 7 of 8 alternating rounds (profiles/r06/dec_prio/)
+  __builtin_amdgcn_s_setprio(1);
+  SlotTileIx six;
+  if constexpr (SLOTS) six = slot_tile_ix(reinterpret_cast<const int32_t *>(p.index), t, rsh, nblk);
+  for (int i = lane; i < 64 * kRowI16 / 4; i += 64) tile[i] = make_uint2(0, 0);
+  __builtin_amdgcn_wave_barrier();
+  // the symbols of the tile into its LDS rows (trash: the lane's row's first pad slot)
+  int pdc;
+  const int P = tile_symbols<kRowI16, SLOTS>(p.sym_len, p.sym_val, p.index, six, t, rsh, nsym, ntiles, nvb * 63, win,
+                                             lane * kRowI16 + 64, lane, pdc);
+  win[lane * kRowI16] = (int16_t)(pdc + wave_incl_sum_i32(d));
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_s_setprio(0);
+  if (!WIN && t == ntiles - 1 && lane == 0)
+    *p.d_status = stream_status<SLOTS>(nsym_raw, nsym, p.sym_len, p.sym_val, t * 64 * 63, P, nblk);
+  if (!RGB && lane >= nvb) return;
+  if constexpr (WIN && !RGB) {
+    // the plane form needs no lane outside the window: only blocks of this wave's row
+    const int wi = (int)(blk / nbx), wj = (int)(blk - (int64_t)wi * nbx);
+    if (wi != wbi || wj < wg.bj0 || wj >= wg.bj1) return;
+  }
+  int qv[64];  // raster [u][v]
+  {
+    const uint2 *row = tile + (lane < nvb ? lane : nvb - 1) * (kRowI16 / 4);
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+      const uint2 x = row[k];
+      qv[ZZ[4 * k]] = (int)(int16_t)(x.x & 0xFFFFu);
+      qv[ZZ[4 * k + 1]] = (int)(int16_t)(x.x >> 16);
+      qv[ZZ[4 * k + 2]] = (int)(int16_t)(x.y & 0xFFFFu);
+      qv[ZZ[4 * k + 3]] = (int)(int16_t)(x.y >> 16);
+    }
+  }
+  const int64_t blk_c = lane < nvb ? blk : t * 64 + nvb - 1;  // RGB: the dead lanes redo the last block
+  const int bi = (int)(blk_c / nbx), bj = (int)(blk_c - (int64_t)bi * nbx);
+  if constexpr (RGB || PITCH) {
+    uint32_t px[16];
+    idct_block_px<TABLE>(qv, px);
+    if constexpr (RGB && WIN) {
+      colour_block<true>(px, bi, bj, nbx, H / 8, lane, lane < nvb, cr, cb, p.out, ostride, wg, wbi);
+    } else if constexpr (RGB) {
+      colour_block<false, PITCH>(px, bi, bj, nbx, H / 8, lane, lane < nvb, cr, cb, p.out, ostride, NoWin{}, 0, cpitch);
+    } else {
+      uint8_t *o = p.out + (int64_t)bi * 8 * ostride + bj * 8;
+#pragma unroll
+      for (int rr = 0; rr < 8; ++rr) {
+        uint32_t *o32 = reinterpret_cast<uint32_t *>(o + rr * ostride);
+        o32[0] = px[2 * rr];
+        o32[1] = px[2 * rr + 1];
+      }
+    }
+  } else if constexpr (WIN) {
+    idct_block_store<TABLE, true>(qv, H, W, bi * 8 - wg.oy, bj * 8 - wg.ox, p.out, ostride);
+  } else {
+    idct_block_store<TABLE, FAST>(qv, H, W, bi * 8, bj * 8, p.out, ostride);
+  }
+}
 // SLOTS: the symbols in the slot layout (slots.h), `index` the close's int32 record
 // index, rsh = log2 records per 64-block tile.
 // WIN: the window form (hic_rle_decode_idct_*_window).  The launch covers the blocks
@@ -501,17 +586,10 @@ struct DecPlane {
 //    No wave of a window launch writes the whole-stream completeness value: a window
 //    does not see the whole stream.
 template <int TABLE, bool FAST, bool RGB = false, bool SLOTS = false, bool WIN = false>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HIC_DEC_WPE))) void k_rld_idct_indexed(const uint8_t *__restrict__ sym_len_a,
-                                                          const int16_t *__restrict__ sym_val_a,
-                                                          const int64_t *__restrict__ d_nsym_a,
-                                                          const int32_t *__restrict__ dc_diff_a,
-                                                          const int64_t *__restrict__ index_a, int H, int W, int nbx,
-                                                          int64_t nblk, uint8_t *__restrict__ out_a, int64_t ostride,
-                                                          int64_t *__restrict__ d_status_a,
-                                                          const uint8_t *__restrict__ cr = nullptr,
-                                                          const uint8_t *__restrict__ cb = nullptr,
-                                                          DecPlane second = DecPlane{}, int rsh = 0,
-                                                          WinArg<WIN> wg = WinArg<WIN>{}) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HIC_DEC_WPE))) void k_rld_idct_indexed(
+    DecPlane first, int H, int W, int nbx, int64_t nblk, int64_t ostride, const uint8_t *__restrict__ cr = nullptr,
+    const uint8_t *__restrict__ cb = nullptr, DecPlane second = DecPlane{}, int rsh = 0,
+    WinArg<WIN> wg = WinArg<WIN>{}) {
   static_assert(!RGB || (TABLE == 0 && FAST), "the RGB form decodes whole-block luma planes");
   static_assert(!WIN || FAST, "a window holds whole blocks");
   __shared__ uint2 s_tile[4][64 * kRowI16 / 4];
@@ -547,100 +625,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HIC_DEC_WPE
       return;
     }
   }
-  const uint8_t *__restrict__ sym_len = b ? second.sym_len : sym_len_a;
-  const int16_t *__restrict__ sym_val = b ? second.sym_val : sym_val_a;
-  const int64_t *__restrict__ d_nsym = b ? second.d_nsym : d_nsym_a;
-  const int32_t *__restrict__ dc_diff = b ? second.dc_diff : dc_diff_a;
-  const int64_t *__restrict__ index = b ? second.index : index_a;
-  uint8_t *__restrict__ out = b ? second.out : out_a;
-  int64_t *__restrict__ d_status = b ? second.d_status : d_status_a;
-  uint2 *tile = s_tile[wv];
-  int16_t *win = reinterpret_cast<int16_t *>(tile);
-  const int64_t nsym_raw = *d_nsym, nsym = nsym_raw > 0 ? nsym_raw : 0;
-  if constexpr (WIN) {
-    if (wfirst && lane == 0) *d_status = nsym_raw < 1 ? -1 : wg.n_ac;
-    if (nsym_raw < 1) return;  // a failed encode's count: nothing is decoded or stored
-  }
-  const int nvb = (int)(nblk - t * 64 < 64 ? nblk - t * 64 : 64);
-  const int64_t blk = t * 64 + lane;
-  // loads that depend on nothing else go out before the zero-fill: this lane's DC
-  // difference and (slot layout) the tile's record index
-  const int d = lane < nvb ? dc_diff[blk] : 0;
-  // the gather (index, symbol loads, LDS scatter) at issue priority 1 over the
-  // SIMD's waves in their IDCT / colour: 16K decode 0.713-0.766 vs 0.749-0.807 ms,
-  // faster in 7 of 8 alternating rounds (profiles/r06/dec_prio/)
-  __builtin_amdgcn_s_setprio(1);
-  SlotTileIx six;
-  if constexpr (SLOTS) six = slot_tile_ix(reinterpret_cast<const int32_t *>(index), t, rsh, nblk);
-  for (int i = lane; i < 64 * kRowI16 / 4; i += 64) tile[i] = make_uint2(0, 0);
-  __builtin_amdgcn_wave_barrier();
-  const int64_t tb0 = t * 64 * 63;
-  const int span = nvb * 63;
-  // the symbols of the tile into its LDS rows (trash: the lane's row's first pad slot)
-  int P, pdc;
-  if constexpr (SLOTS) {
-    P = slots_gather_tile<kRowI16>(sym_len, sym_val, six, t, rsh, span, win, lane * kRowI16 + 64, lane);
-    pdc = six.r[0].z;
-  } else {
-    const int64_t o0 = index[3 * t] < nsym ? index[3 * t] : nsym;
-    const int64_t o1 = t + 1 < ntiles ? (index[3 * (t + 1)] < nsym ? index[3 * (t + 1)] : nsym) : nsym;
-    P = gather_tile<kRowI16, HIC_DEC_G, HIC_DEC_PF>(sym_len, sym_val, o0, o1, nsym, (int)(index[3 * t + 1] + 1 - tb0),
-                                                    span, win, lane * kRowI16 + 64, lane);
-    pdc = (int)index[3 * t + 2];
-  }
-  win[lane * kRowI16] = (int16_t)(pdc + wave_incl_sum_i32(d));
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_s_setprio(0);
-  if (!WIN && t == ntiles - 1 && lane == 0) {
-    // (a slot-layout stream is whole by construction: its EOB zero-fills the rest)
-    const int64_t total = tb0 + (int64_t)P, n_ac = nblk * 63;
-    const bool eob = SLOTS || (nsym > 0 && sym_len[nsym - 1] == 0 && sym_val[nsym - 1] == 0);
-    *d_status = nsym_raw < 1 ? -1 : ((eob && (SLOTS || total <= n_ac)) ? n_ac : total);
-  }
-  if (!RGB && lane >= nvb) return;
-  if constexpr (WIN && !RGB) {
-    // the plane form needs no lane outside the window: only blocks of this wave's row
-    const int wi = (int)(blk / nbx), wj = (int)(blk - (int64_t)wi * nbx);
-    if (wi != wbi || wj < wg.bj0 || wj >= wg.bj1) return;
-  }
-  int qv[64];  // raster [u][v]
-  {
-    const uint2 *row = tile + (lane < nvb ? lane : nvb - 1) * (kRowI16 / 4);
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-      const uint2 x = row[k];
-      qv[ZZ[4 * k]] = (int)(int16_t)(x.x & 0xFFFFu);
-      qv[ZZ[4 * k + 1]] = (int)(int16_t)(x.x >> 16);
-      qv[ZZ[4 * k + 2]] = (int)(int16_t)(x.y & 0xFFFFu);
-      qv[ZZ[4 * k + 3]] = (int)(int16_t)(x.y >> 16);
-    }
-  }
-  const int64_t blk_c = lane < nvb ? blk : t * 64 + nvb - 1;  // RGB: the dead lanes redo the last block
-  const int bi = (int)(blk_c / nbx), bj = (int)(blk_c - (int64_t)bi * nbx);
-  if (RGB) {
-    uint32_t px[16];
-    idct_block_px<TABLE>(qv, px);
-    if constexpr (WIN) colour_block<true>(px, bi, bj, nbx, H / 8, lane, lane < nvb, cr, cb, out, ostride, wg, wbi);
-    else colour_block(px, bi, bj, nbx, H / 8, lane, lane < nvb, cr, cb, out, ostride);
-  } else if constexpr (WIN) {
-    idct_block_store<TABLE, true>(qv, H, W, bi * 8 - wg.oy, bj * 8 - wg.ox, out, ostride);
-  } else {
-    idct_block_store<TABLE, FAST>(qv, H, W, bi * 8, bj * 8, out, ostride);
-  }
+  const DecPlane &f = first, &s = second;  // (a select of the whole by-value struct goes through scratch)
+  const DecPlane pl{b ? s.sym_len : f.sym_len, b ? s.sym_val : f.sym_val, b ? s.d_nsym : f.d_nsym,
+                    b ? s.dc_diff : f.dc_diff, b ? s.index : f.index, b ? s.out : f.out, b ? s.d_status : f.d_status};
+  decode_tile<TABLE, FAST, RGB, SLOTS, WIN>(pl, t, s_tile[wv], lane, H, W, nbx, nblk, ostride, cr, cb, rsh, wg, wbi,
+                                            wfirst);
 }
 
-// The batched form (hic_decode420_batch_u8, decode_batch.h): per wave exactly what
-// k_rld_idct_indexed<TABLE, true, RGB, SLOTS> does for one tile, the plane's pointers
-// read from the batch's table in device memory.  One wave per tile, per-wave LDS and
+// The batched form (hic_decode420_batch_u8, decode_batch.h): per wave the decode_tile
+// of k_rld_idct_indexed<TABLE, true, RGB, SLOTS>, the plane's pointers read from the
+// batch's table in device memory.  One wave per tile, per-wave LDS and
 // only wave barriers, so the four waves of a workgroup may belong to different planes
 // and to different images.  With g = blockIdx.x * 4 + wave and T = a.tiles waves per
 // image (RGB: Y's tiles; else Cr's tiles, then Cb's): image g / T, plane (g % T) /
 // ntiles, tile (g % T) % ntiles; a wave with g >= n * T returns.  All of it is
 // wave-uniform and kept in SGPRs, so the table entry is read by scalar loads.  The
-// body is a copy of the one-image kernel's (sharing it through a function changes the
-// existing kernels' register allocation, profiles/r14/decode_batch/isa_identity.txt).
-// The chroma planes' rows are a.cstride bytes apart (>= W / 2, a multiple of 4): the
-// plane form stores dwords, the RGB form loads dwords.
+// records per tile are compile-time here (RSH).  The chroma planes' rows are a.cstride
+// bytes apart (>= W / 2, a multiple of 4): plane form dword stores, RGB form dword loads.
 struct DecBatchArgs {
   const DecBatchEntry *tab;
   uint32_t total, tiles;  // n * T, T
@@ -664,78 +665,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HIC_DEC_WPE
   typedef const __attribute__((address_space(4))) DecBatchEntry centry;
   centry *ent = (centry *)(uintptr_t)(a.tab + img);
   const int ch = RGB ? 0 : (second ? 2 : 1);
-  const uint8_t *__restrict__ sym_len = ent->c[ch].sym_len;
-  const int16_t *__restrict__ sym_val = ent->c[ch].sym_val;
-  const int64_t *__restrict__ d_nsym = ent->c[ch].d_nsym;
-  const int32_t *__restrict__ dc_diff = ent->c[ch].dc_diff;
-  const int64_t *__restrict__ index = static_cast<const int64_t *>(ent->c[ch].index);
-  uint8_t *__restrict__ out = ent->c[ch].out;
-  int64_t *__restrict__ d_status = ent->c[ch].d_status;
-  const int nbx = a.nbx, rsh = RGB ? 0 : 1;
-  const int64_t nblk = a.nblk, ntiles = a.ntiles;
-  uint2 *tile = s_tile[wv];
-  int16_t *win = reinterpret_cast<int16_t *>(tile);
-  const int64_t nsym_raw = *d_nsym, nsym = nsym_raw > 0 ? nsym_raw : 0;
-  const int nvb = (int)(nblk - t * 64 < 64 ? nblk - t * 64 : 64);
-  const int64_t blk = t * 64 + lane;
-  const int d = lane < nvb ? dc_diff[blk] : 0;
-  __builtin_amdgcn_s_setprio(1);
-  SlotTileIx six;
-  if constexpr (SLOTS) six = slot_tile_ix(reinterpret_cast<const int32_t *>(index), t, rsh, nblk);
-  for (int i = lane; i < 64 * kRowI16 / 4; i += 64) tile[i] = make_uint2(0, 0);
-  __builtin_amdgcn_wave_barrier();
-  const int64_t tb0 = t * 64 * 63;
-  const int span = nvb * 63;
-  int P, pdc;
-  if constexpr (SLOTS) {
-    P = slots_gather_tile<kRowI16>(sym_len, sym_val, six, t, rsh, span, win, lane * kRowI16 + 64, lane);
-    pdc = six.r[0].z;
-  } else {
-    const int64_t o0 = index[3 * t] < nsym ? index[3 * t] : nsym;
-    const int64_t o1 = t + 1 < ntiles ? (index[3 * (t + 1)] < nsym ? index[3 * (t + 1)] : nsym) : nsym;
-    P = gather_tile<kRowI16, HIC_DEC_G, HIC_DEC_PF>(sym_len, sym_val, o0, o1, nsym, (int)(index[3 * t + 1] + 1 - tb0),
-                                                    span, win, lane * kRowI16 + 64, lane);
-    pdc = (int)index[3 * t + 2];
-  }
-  win[lane * kRowI16] = (int16_t)(pdc + wave_incl_sum_i32(d));
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_s_setprio(0);
-  if (t == ntiles - 1 && lane == 0) {
-    const int64_t total = tb0 + (int64_t)P, n_ac = nblk * 63;
-    const bool eob = SLOTS || (nsym > 0 && sym_len[nsym - 1] == 0 && sym_val[nsym - 1] == 0);
-    *d_status = nsym_raw < 1 ? -1 : ((eob && (SLOTS || total <= n_ac)) ? n_ac : total);
-  }
-  if (!RGB && lane >= nvb) return;
-  int qv[64];  // raster [u][v]
-  {
-    const uint2 *row = tile + (lane < nvb ? lane : nvb - 1) * (kRowI16 / 4);
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-      const uint2 x = row[k];
-      qv[ZZ[4 * k]] = (int)(int16_t)(x.x & 0xFFFFu);
-      qv[ZZ[4 * k + 1]] = (int)(int16_t)(x.x >> 16);
-      qv[ZZ[4 * k + 2]] = (int)(int16_t)(x.y & 0xFFFFu);
-      qv[ZZ[4 * k + 3]] = (int)(int16_t)(x.y >> 16);
-    }
-  }
-  const int64_t blk_c = lane < nvb ? blk : t * 64 + nvb - 1;  // RGB: the dead lanes redo the last block
-  const int bi = (int)(blk_c / nbx), bj = (int)(blk_c - (int64_t)bi * nbx);
-  uint32_t px[16];
-  idct_block_px<TABLE>(qv, px);
-  if constexpr (RGB) {
-    const uint8_t *__restrict__ cr = ent->c[1].out;
-    const uint8_t *__restrict__ cb = ent->c[2].out;
-    colour_block<false, true>(px, bi, bj, nbx, a.H / 8, lane, lane < nvb, cr, cb, out, a.ostride, NoWin{}, 0, a.cstride);
-  } else {
-    // (rows 4 bytes aligned: the pitch is a multiple of 4, not of 8)
-    uint8_t *o = out + (int64_t)bi * 8 * a.ostride + bj * 8;
-#pragma unroll
-    for (int rr = 0; rr < 8; ++rr) {
-      uint32_t *o32 = reinterpret_cast<uint32_t *>(o + rr * a.ostride);
-      o32[0] = px[2 * rr];
-      o32[1] = px[2 * rr + 1];
-    }
-  }
+  const DecPlane pl{ent->c[ch].sym_len, ent->c[ch].sym_val, ent->c[ch].d_nsym, ent->c[ch].dc_diff,
+                    static_cast<const int64_t *>(ent->c[ch].index), ent->c[ch].out, ent->c[ch].d_status};
+  const uint8_t *cr = RGB ? ent->c[1].out : nullptr, *cb = RGB ? ent->c[2].out : nullptr;
+  decode_tile<TABLE, true, RGB, SLOTS, false, true, RGB ? 0 : 1>(pl, t, s_tile[wv], lane, a.H, a.W, a.nbx, a.nblk,
+                                                                 a.ostride, cr, cb, 0, NoWin{}, 0, false, a.cstride);
 }
 
 // Production forward kernel for aligned planes: up to three planes per launch
@@ -1290,8 +1224,8 @@ static int launch_rld_idct(const DecLaunch &d, void *stream) {
   const DecPlane &a = d.p[0], second = d.nplanes > 1 ? d.p[1] : DecPlane{};
   const int rsh = d.slots && d.records_per_tile == 2 ? 1 : 0;
 #define HIC_DEC(T, F, R, S)                                                                                         \
-  hipLaunchKernelGGL((k_rld_idct_indexed<T, F, R, S>), grid, block, 0, s, a.sym_len, a.sym_val, a.d_nsym, a.dc_diff, \
-                     a.index, (int)d.H, (int)d.W, nbx, nblk, a.out, d.out_stride, a.d_status, d.cr, d.cb, second, rsh)
+  hipLaunchKernelGGL((k_rld_idct_indexed<T, F, R, S>), grid, block, 0, s, a, (int)d.H, (int)d.W, nbx, nblk, \
+                     d.out_stride, d.cr, d.cb, second, rsh)
 #define HIC_DEC_PLANES(S)                                      \
   do {                                                         \
     if (d.table_id == 0 && fast) HIC_DEC(0, true, false, S);   \
@@ -1470,9 +1404,8 @@ static int launch_rld_idct_window(const DecLaunch &d, int kind, const hic_window
   const DecPlane &a = d.p[0], second = d.nplanes > 1 ? d.p[1] : DecPlane{};
   const int rsh = d.slots && d.records_per_tile == 2 ? 1 : 0;
 #define HIC_DEC_WIN(T, R, S)                                                                                      \
-  hipLaunchKernelGGL((k_rld_idct_indexed<T, true, R, S, true>), grid, block, 0, s, a.sym_len, a.sym_val, a.d_nsym, \
-                     a.dc_diff, a.index, (int)pH, (int)pW, nbx, nblk, a.out, d.out_stride, a.d_status, d.cr, d.cb, \
-                     second, rsh, g)
+  hipLaunchKernelGGL((k_rld_idct_indexed<T, true, R, S, true>), grid, block, 0, s, a, (int)pH, (int)pW, nbx, nblk, \
+                     d.out_stride, d.cr, d.cb, second, rsh, g)
   if (d.rgb && d.slots) HIC_DEC_WIN(0, true, true);
   else if (d.rgb) HIC_DEC_WIN(0, true, false);
   else if (d.slots) HIC_DEC_WIN(1, false, true);

@@ -637,22 +637,16 @@ inline int64_t rle_ws_words(int64_t nrec) {
   const int64_t n = nrec > 0 ? nrec : 1;
   return 5 * n + 3 * ((n + kScan16T - 1) / kScan16T) + 8;
 }
+// Partition p of job J: the body of k_rle_scan16b and of the batch's
+// k_rle_scan16_table.  (A job built with stitch = nullptr, as the table's whole
+// images are, folds to p0 = -1 and an unconditional EOB at compile time.)
 // SLOTS (the slot layout's close, slots.h): each record's first symbol length, its
 // first block's DC difference, and its index entry, from the same exclusive scan.
 template <bool SLOTS>
-__global__ __launch_bounds__(kScan16T) void k_rle_scan16b(RleJobs16 jobs, uint32_t epoch) {
+__device__ __forceinline__ void scan16_partition(const RleJob16 &J, int64_t p, int M, uint32_t epoch) {
   __shared__ Agg s_wave[kScan16T / 64 + 1];
   __shared__ Agg s_pre;
   __shared__ int s_fail;
-  // workgroup -> (job, partition)
-  int jb = 0;
-  int64_t p = blockIdx.x;
-  while (jb + 1 < jobs.n && p >= (jobs.j[jb].nrec + kScan16T - 1) / kScan16T) {
-    p -= (jobs.j[jb].nrec + kScan16T - 1) / kScan16T;
-    ++jb;
-  }
-  const RleJob16 &J = jobs.j[jb];
-  const int M = jobs.M;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t nt = J.nrec, np = (nt + kScan16T - 1) / kScan16T;
   const int64_t *tiles = J.ws;
@@ -767,6 +761,24 @@ __global__ __launch_bounds__(kScan16T) void k_rle_scan16b(RleJobs16 jobs, uint32
   // every partition's write, so the report cannot be overwritten by a total)
   if (s_fail && threadIdx.x == 0) put_granule(gran + 3 * np, 1, tag);
 }
+template <bool SLOTS>
+__global__ __launch_bounds__(kScan16T) void k_rle_scan16b(RleJobs16 jobs, uint32_t epoch) {
+  // workgroup -> (job, partition)
+  int jb = 0;
+  int64_t p = blockIdx.x;
+  while (jb + 1 < jobs.n && p >= (jobs.j[jb].nrec + kScan16T - 1) / kScan16T) {
+    p -= (jobs.j[jb].nrec + kScan16T - 1) / kScan16T;
+    ++jb;
+  }
+  scan16_partition<SLOTS>(jobs.j[jb], p, jobs.M, epoch);
+}
+// The scan's failure report (sticky): a channel whose failure granule, the one after
+// its np partitions' hand-off granules, carries this epoch's tag gets the timeout count.
+__device__ void scan_fold_timeout(const int64_t *ws, int64_t nrec, int64_t np, uint32_t epoch, int64_t *d_count) {
+  int64_t f;
+  if (get_granule(reinterpret_cast<const uint64_t *>(ws + 5 * nrec) + 3 * np, (epoch << 2) | 1u, f))
+    *d_count = HIC_COUNT_SCAN_TIMEOUT;
+}
 
 template <int MF>
 __global__ __launch_bounds__(256) void k_rle_emit16b(RleJobs16 jobs) {
@@ -780,12 +792,9 @@ __global__ __launch_bounds__(256) void k_rle_emit16b(RleJobs16 jobs) {
   const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int64_t nwaves = (int64_t)gridDim.x * 4;
   const int M = jobs.M;
-  if (blockIdx.x == 0 && threadIdx.x < jobs.n) {  // the scan's failure report (sticky)
+  if (blockIdx.x == 0 && threadIdx.x < jobs.n) {
     const RleJob16 &J = jobs.j[threadIdx.x];
-    const int64_t np = (J.nrec + kScan16T - 1) / kScan16T;
-    int64_t f;
-    if (get_granule(reinterpret_cast<const uint64_t *>(J.ws + 5 * J.nrec) + 3 * np, (jobs.epoch << 2) | 1u, f))
-      *J.d_count = HIC_COUNT_SCAN_TIMEOUT;
+    scan_fold_timeout(J.ws, J.nrec, (J.nrec + kScan16T - 1) / kScan16T, jobs.epoch, J.d_count);
   }
   int64_t g = (int64_t)blockIdx.x * 4 + wv;
   if (g >= jobs.total_tiles) return;  // wave-uniform
@@ -896,10 +905,7 @@ __global__ __launch_bounds__(256) void k_rle_emit16b(RleJobs16 jobs) {
 __global__ void k_rle_scan_fold(RleJobs16 jobs) {
   if (threadIdx.x < jobs.n) {
     const RleJob16 &J = jobs.j[threadIdx.x];
-    const int64_t np = (J.nrec + kScan16T - 1) / kScan16T;
-    int64_t f;
-    if (get_granule(reinterpret_cast<const uint64_t *>(J.ws + 5 * J.nrec) + 3 * np, (jobs.epoch << 2) | 1u, f))
-      *J.d_count = HIC_COUNT_SCAN_TIMEOUT;
+    scan_fold_timeout(J.ws, J.nrec, (J.nrec + kScan16T - 1) / kScan16T, jobs.epoch, J.d_count);
   }
 }
 
@@ -1732,25 +1738,14 @@ __global__ __launch_bounds__(256) void k_rld_indexed16(const uint8_t *__restrict
 #pragma unroll
   for (int k = 0; k < 8; ++k) tile[64 * k + lane] = make_uint4(0, 0, 0, 0);
   __builtin_amdgcn_wave_barrier();
-  const int64_t tb0 = t * 64 * 63;                    // the tile's first AC position
   const int nvb = (int)(nblk - t * 64 < 64 ? nblk - t * 64 : 64);
   const int span = nvb * 63;                           // its AC positions
-  int P = 0, pdc;
-  if constexpr (SLOTS) {
-    // the tile's records, each from its own slot (trash slots: the 64 after the tile)
-    const SlotTileIx six = slot_tile_ix(reinterpret_cast<const int32_t *>(index), t, rsh, nblk);
-    P = slots_gather_tile<64>(sym_len, sym_val, six, t, rsh, span, win, 64 * 64 + lane, lane);
-    pdc = six.r[0].z;
-  } else {
-    const int64_t o0 = index[3 * t] < nsym ? index[3 * t] : nsym;
-    const int64_t o1 = t + 1 < ntiles ? (index[3 * (t + 1)] < nsym ? index[3 * (t + 1)] : nsym) : nsym;
-    // P: the position after the previous tile's last symbol, relative to the tile (a
-    // carried run can start far before it; every AC position of the stream fits int32).
-    // Trash slots (never read): the 64 after the tile.
-    P = gather_tile<64, HIC_DEC_G, HIC_DEC_PF>(sym_len, sym_val, o0, o1, nsym, (int)(index[3 * t + 1] + 1 - tb0), span,
-                                               win, 64 * 64 + lane, lane);
-    pdc = (int)index[3 * t + 2];
-  }
+  // the tile's symbols (trash slots, never read: the 64 after the tile)
+  SlotTileIx six;
+  if constexpr (SLOTS) six = slot_tile_ix(reinterpret_cast<const int32_t *>(index), t, rsh, nblk);
+  int pdc;
+  const int P = tile_symbols<64, SLOTS>(sym_len, sym_val, index, six, t, rsh, nsym, ntiles, span, win, 64 * 64 + lane,
+                                        lane, pdc);
   // DC: the previous block's value plus this tile's differences
   const int64_t b = t * 64 + lane;
   const int d = lane < nvb ? dc_diff[b] : 0;
@@ -1766,27 +1761,18 @@ __global__ __launch_bounds__(256) void k_rld_indexed16(const uint8_t *__restrict
       *o = u32x4{x.x, x.y, x.z, x.w};
     }
   }
-  if (t == ntiles - 1 && lane == 0) {
-    // codec.decode_run_length's length: an EOB zero-fills to the end (a slot-layout
-    // stream is whole by construction)
-    const int64_t total = tb0 + (int64_t)P, n_ac = nblk * 63;
-    const bool eob = SLOTS || (nsym > 0 && sym_len[nsym - 1] == 0 && sym_val[nsym - 1] == 0);
-    *d_status = nsym_raw < 1 ? -1 : ((eob && (SLOTS || total <= n_ac)) ? n_ac : total);
-  }
+  if (t == ntiles - 1 && lane == 0)
+    *d_status = stream_status<SLOTS>(nsym_raw, nsym, sym_len, sym_val, t * 64 * 63, P, nblk);
 }
-
 
 // The close of a batch of slot-layout images (hic_rle_slots_close_batch, slots_batch.h):
 // all 3 n channels in one launch.  The images share a shape, so workgroup -> (image,
-// channel, partition) is arithmetic; the job comes from the image's table entry.
+// channel, partition) is arithmetic; scan16_partition<true>'s job comes from the entry.
 // A partition's hand-offs look back only to earlier partitions of its own channel,
 // which have smaller workgroup indices, and workgroups are dispatched in index order:
 // whatever a partition waits for is resident or done, so a grid larger than the
 // resident set cannot deadlock -- and the spin is bounded in any case (the failure
 // granule, folded into the count by k_rle_scan_fold_table).
-// The body is k_rle_scan16b<true>'s, written out again and not shared: with the body
-// in a __device__ function both callers inline, the existing instantiations' register
-// allocation changed (tools/check/kernel_isa_diff.py), and they are to stay as they are.
 struct ScanTable {
   const SlotBatchEntry *tab;
   int64_t nblk[3];
@@ -1794,13 +1780,7 @@ struct ScanTable {
   int parts_image, n, M;
   uint32_t epoch;
 };
-// (templates only so that they are instantiated, and so emitted, after every existing
-// kernel: the block labels of those then keep their numbers in the listing)
-template <int = 0>
 __global__ __launch_bounds__(kScan16T) void k_rle_scan16_table(ScanTable T) {
-  __shared__ Agg s_wave[kScan16T / 64 + 1];
-  __shared__ Agg s_pre;
-  __shared__ int s_fail;
   // workgroup -> (image, channel, partition)
   const int b = (int)blockIdx.x, img = b / T.parts_image;
   int pp = b - img * T.parts_image, ch = 0;
@@ -1812,141 +1792,23 @@ __global__ __launch_bounds__(kScan16T) void k_rle_scan16_table(ScanTable T) {
       ch = 2;
     }
   }
-  const int64_t p = pp;
-  const SlotBatchChan &c = T.tab[img].c[ch];
-  struct {
-    int64_t nrec, nblk, bpr, cap;
-    int64_t *ws, *d_count;
-    uint8_t *slot_len, *sym_len;
-    int16_t *sym_val;
-    int32_t *dc_diff, *rdc, *sidx;
-  } const J{T.nrec[ch], T.nblk[ch], ch ? 32 : 64, c.cap, c.ws, c.d_count, c.slot_len, c.sym_len,
-            c.sym_val, c.dc_diff, c.rdc, c.sidx};
-  const int M = T.M;
-  const uint32_t epoch = T.epoch;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int64_t nt = J.nrec, np = (nt + kScan16T - 1) / kScan16T;
-  const int64_t *tiles = J.ws;
-  int64_t *offs = J.ws + rle_offs_word(nt);
-  uint64_t *gran = reinterpret_cast<uint64_t *>(J.ws + 5 * nt);  // 3 per partition
-  const uint32_t tag = (epoch << 2) | 1u;
-  const int64_t t = p * kScan16T + threadIdx.x;
-  const Agg rec = t < nt ? Agg{tiles[t * 3 + 0], tiles[t * 3 + 1], tiles[t * 3 + 2]} : Agg{-1, -1, 0};
-  // workgroup inclusive scan of the partition's tile records
-  Agg incl = rec;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const Agg o = agg_shfl_up(incl, d);
-    if (lane >= d) incl = agg_combine(o, incl, M);
-  }
-  if (lane == 63) s_wave[wave] = incl;
-  if (threadIdx.x == 0) s_fail = 0;
-  __syncthreads();
-  if (wave == 0) {
-    constexpr int NW = kScan16T / 64;
-    Agg it = lane < NW ? s_wave[lane] : Agg{-1, -1, 0};
-#pragma unroll
-    for (int d = 1; d < NW; d <<= 1) {
-      const Agg o = agg_shfl_up(it, d);
-      if (lane >= d) it = agg_combine(o, it, M);
-    }
-    Agg ex = agg_shfl_up(it, 1);
-    if (lane == 0) ex = Agg{-1, -1, 0};
-    if (lane < NW) s_wave[lane] = ex;
-    if (lane == NW - 1) {
-      s_wave[NW] = it;  // the partition's aggregate: publish it
-      put_granule(gran + 3 * p + 0, it.first, tag);
-      put_granule(gran + 3 * p + 1, it.last, tag);
-      put_granule(gran + 3 * p + 2, it.cnt, tag);
-    }
-    // fold the aggregates of the earlier partitions (lane q < p polls partition q)
-    Agg pre{-1, -1, 0};
-    for (int64_t q0 = 0; q0 < p; q0 += 64) {
-      const int64_t q = q0 + lane;
-      Agg a{-1, -1, 0};
-      if (q < p) {
-        bool ok = false;
-        for (int spin = 0; spin < (1 << 22) && !ok; ++spin) {
-          int64_t f, l, c;
-          ok = (int)get_granule(gran + 3 * q + 0, tag, f) & (int)get_granule(gran + 3 * q + 1, tag, l) &
-               get_granule(gran + 3 * q + 2, tag, c);
-          if (ok) a = Agg{f, l, c};
-          else __builtin_amdgcn_s_sleep(2);
-        }
-        if (!ok) s_fail = 1;
-      }
-      // the window's ordered total by a wave scan (agg_combine is associative):
-      // log2(64) steps instead of one serial combine per earlier partition (the
-      // 16K image has 512 partitions per channel, and its last ones folded them all)
-      Agg wi = a;
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const Agg o = agg_shfl_up(wi, d);
-        if (lane >= d) wi = agg_combine(o, wi, M);
-      }
-      const int lastl = (int)(p - q0 < 64 ? p - q0 - 1 : 63);
-      pre = agg_combine(pre, Agg{__shfl(wi.first, lastl, 64), __shfl(wi.last, lastl, 64), __shfl(wi.cnt, lastl, 64)}, M);
-    }
-    if (lane == 0) s_pre = pre;
-  }
-  __syncthreads();
-  const int64_t p0 = -1;  // virtual last nonzero before the stream (a whole image: no carry)
-  Agg excl = agg_shfl_up(incl, 1);
-  if (lane == 0) excl = Agg{-1, -1, 0};
-  excl = agg_combine(agg_combine(s_pre, s_wave[wave], M), excl, M);
-  if (t < nt) {
-    offs[t * 2 + 0] = excl.last >= 0 ? excl.cnt + syms_for_run(excl.first - p0 - 1, M) : 0;
-    offs[t * 2 + 1] = excl.last >= 0 ? excl.last : p0;
-  }
-  if (t < nt) {
-    // the record's first nonzero continues the zero run since the previous record's
-    // last nonzero: its fillers and its first symbol's length (written as 0 by the
-    // fused kernel); P: the record-relative position the run's remainder starts after
-    const int64_t prv = excl.last >= 0 ? excl.last : p0, capr = 63 * J.bpr;
-    int n = 0, P = 0, nf = 0;
-    if (rec.first >= 0) {
-      const int64_t run = rec.first - prv - 1, f = div_run(run, M);
-      const int len0 = (int)(run - f * M);
-      nf = (int)f;
-      n = (int)rec.cnt + 1;
-      P = (int)(rec.first - t * capr) - len0;
-      J.slot_len[t * capr] = (uint8_t)len0;
-    }
-    // codec.differential_coding across the record boundary
-    const int pdc = t > 0 ? J.rdc[t - 1] : 0;
-    if (t > 0) J.dc_diff[t * J.bpr] -= pdc;
-    *reinterpret_cast<int4 *>(J.sidx + 4 * t) = make_int4(n, P, pdc, nf);
-  }
-  if (p == np - 1 && threadIdx.x == 0) {  // the channel's last partition closes the stream
-    const Agg all = agg_combine(s_pre, s_wave[kScan16T / 64], M);
-    const int64_t last = all.last >= 0 ? all.last : p0;
-    const int64_t n_ac = J.nblk * 63;
-    int64_t total = all.last >= 0 ? all.cnt + syms_for_run(all.first - p0 - 1, M) : 0;
-    if (!(n_ac > 0 && last == n_ac - 1)) {
-      if (total < J.cap) {
-        J.sym_len[total] = 0;
-        J.sym_val[total] = 0;
-      }
-      ++total;
-    }
-    *J.d_count = total <= J.cap ? total : -total;
-  }
-  // a hand-off that timed out is reported, not waited for: a tagged failure granule
-  // after the partitions' ones, folded into *d_count by the emit (which runs after
-  // every partition's write, so the report cannot be overwritten by a total)
-  if (s_fail && threadIdx.x == 0) put_granule(gran + 3 * np, 1, tag);
+  // the entry through a constant-address-space pointer: its pointers are then known
+  // global ones although J is filled before the body is inlined (flat accesses else)
+  typedef const __attribute__((address_space(4))) SlotBatchChan cchan;
+  cchan &c = *(cchan *)(uintptr_t)&T.tab[img].c[ch];
+  RleJob16 J{};  // (stitch null: a whole image, no carry, always an EOB)
+  J.nblk = T.nblk[ch], J.nrec = T.nrec[ch], J.bpr = ch ? 32 : 64;
+  J.ws = c.ws, J.rdc = c.rdc, J.slot_len = c.slot_len, J.dc_diff = c.dc_diff, J.sidx = c.sidx;
+  J.sym_len = c.sym_len, J.sym_val = c.sym_val, J.cap = c.cap, J.d_count = c.d_count;
+  scan16_partition<true>(J, pp, T.M, T.epoch);
 }
 // k_rle_scan_fold for the table: thread -> (image, channel)
-template <int = 0>
 __global__ __launch_bounds__(256) void k_rle_scan_fold_table(ScanTable T) {
   const int t = (int)(blockIdx.x * blockDim.x + threadIdx.x);
   if (t >= 3 * T.n) return;
   const int img = t / 3, ch = t - 3 * img;
   const SlotBatchChan &c = T.tab[img].c[ch];
-  const int64_t nrec = T.nrec[ch];
-  int64_t f;
-  if (get_granule(reinterpret_cast<const uint64_t *>(c.ws + 5 * nrec) + 3 * T.parts[ch], (T.epoch << 2) | 1u, f))
-    *c.d_count = HIC_COUNT_SCAN_TIMEOUT;
+  scan_fold_timeout(c.ws, T.nrec[ch], T.parts[ch], T.epoch, c.d_count);
 }
 
 }  // namespace
@@ -2168,6 +2030,21 @@ extern "C" size_t hic_rle_slots_workspace_bytes(int64_t nblk, int records_per_ti
   return (size_t)(rle_ws_words(nrec) + (nrec + 1) / 2 + 2) * sizeof(int64_t);
 }
 
+// What every taker of a hic_slot_job checks of it; who: "job 1", "image 0 job 2"
+static int check_slot_job(const hic_slot_job &a, const char *who) {
+  if (!a.slot_len || !a.slot_val || !a.dc_diff || !a.d_index || !a.workspace || !a.d_count || !a.sym_len || !a.sym_val)
+    return arg_error("%s: null pointer", who);
+  if (a.nblk <= 0 || a.nblk > (int64_t)INT32_MAX / 63) return arg_error("%s: nblk", who);
+  if (a.records_per_tile != 1 && a.records_per_tile != 2)
+    return arg_error("%s: records_per_tile must be 1 or 2", who);
+  const int64_t bpr = 64 / a.records_per_tile;
+  if (a.nblk % bpr) return arg_error("%s: nblk must be a multiple of %lld (whole records)", who, (long long)bpr);
+  const int64_t need = (int64_t)hic_rle_slots_workspace_bytes(a.nblk, (int)a.records_per_tile);
+  if (a.workspace_bytes < need)
+    return arg_error("%s: workspace of %lld bytes, %lld needed", who, (long long)a.workspace_bytes, (long long)need);
+  return HIC_OK;
+}
+
 // hic_slot_job[n] -> the scan / compaction jobs (validated, nothing launched on error)
 static int slot_jobs(int n, const hic_slot_job *jobs, int max_len, RleJobs16 &J) {
   if (n < 1 || n > kMaxJobs || !jobs) return arg_error("1 <= n <= %d jobs", kMaxJobs);
@@ -2177,16 +2054,10 @@ static int slot_jobs(int n, const hic_slot_job *jobs, int max_len, RleJobs16 &J)
   J.M = max_len;
   for (int k = 0; k < n; ++k) {
     const hic_slot_job &a = jobs[k];
-    if (!a.slot_len || !a.slot_val || !a.dc_diff || !a.d_index || !a.workspace || !a.d_count || !a.sym_len ||
-        !a.sym_val)
-      return arg_error("job %d: null pointer", k);
-    if (a.nblk <= 0 || a.nblk > (int64_t)INT32_MAX / 63) return arg_error("job %d: nblk", k);
-    if (a.records_per_tile != 1 && a.records_per_tile != 2) return arg_error("job %d: records_per_tile must be 1 or 2", k);
+    char who[16];
+    snprintf(who, sizeof who, "job %d", k);
+    if (int e = check_slot_job(a, who)) return e;
     const int64_t bpr = 64 / a.records_per_tile;
-    if (a.nblk % bpr) return arg_error("job %d: nblk must be a multiple of %lld (whole records)", k, (long long)bpr);
-    const int64_t need = (int64_t)hic_rle_slots_workspace_bytes(a.nblk, (int)a.records_per_tile);
-    if (a.workspace_bytes < need)
-      return arg_error("job %d: workspace of %lld bytes, %lld needed", k, (long long)a.workspace_bytes, (long long)need);
     RleJob16 &j = J.j[k];
     j = RleJob16{};
     j.nblk = a.nblk;
@@ -2278,19 +2149,14 @@ extern "C" int hic_slots_batch_table(int n, int64_t H, int64_t W, const hic_slot
   for (int i = 0; i < 3 * n; ++i) {
     const hic_slot_job &a = jobs[i];
     const int k = i % 3, rpt = k ? 2 : 1;
-    if (!a.slot_len || !a.slot_val || !a.dc_diff || !a.d_index || !a.workspace || !a.d_count || !a.sym_len ||
-        !a.sym_val)
-      return arg_error("image %d job %d: null pointer", i / 3, k);
     if (a.nblk != h.nblk[k] || a.records_per_tile != rpt)
       return arg_error("image %d job %d: nblk %lld / records_per_tile %lld, expected %lld / %d", i / 3, k,
                        (long long)a.nblk, (long long)a.records_per_tile, (long long)h.nblk[k], rpt);
-    if (a.nblk > (int64_t)INT32_MAX / 63) return arg_error("image %d job %d: nblk", i / 3, k);
+    char who[32];
+    snprintf(who, sizeof who, "image %d job %d", i / 3, k);
+    if (int e = check_slot_job(a, who)) return e;
     if ((reinterpret_cast<uintptr_t>(a.slot_len) | reinterpret_cast<uintptr_t>(a.slot_val)) % 16)
       return arg_error("image %d job %d: slot arrays must be 16-byte aligned", i / 3, k);
-    const int64_t need = (int64_t)hic_rle_slots_workspace_bytes(a.nblk, rpt);
-    if (a.workspace_bytes < need)
-      return arg_error("image %d job %d: workspace of %lld bytes, %lld needed", i / 3, k,
-                       (long long)a.workspace_bytes, (long long)need);
   }
   // no two jobs may share what the launches write per job: sorted by address, a
   // range must end before the next one starts
@@ -2353,9 +2219,9 @@ extern "C" int hic_rle_slots_close_batch(const void *h_table, const void *d_tabl
   T.M = max_len;
   T.epoch = next_epoch();
   hipStream_t s = as_stream(stream);
-  hipLaunchKernelGGL(k_rle_scan16_table<>, dim3((unsigned)(h.n * h.parts_image)), dim3(kScan16T), 0, s, T);
+  hipLaunchKernelGGL(k_rle_scan16_table, dim3((unsigned)(h.n * h.parts_image)), dim3(kScan16T), 0, s, T);
   if (int e = check_launch("k_rle_scan16_table")) return e;
-  hipLaunchKernelGGL(k_rle_scan_fold_table<>, dim3((unsigned)((3 * h.n + 255) / 256)), dim3(256), 0, s, T);
+  hipLaunchKernelGGL(k_rle_scan_fold_table, dim3((unsigned)((3 * h.n + 255) / 256)), dim3(256), 0, s, T);
   return check_launch("k_rle_scan_fold_table");
 }
 

@@ -566,5 +566,41 @@ __device__ __forceinline__ int slots_gather_tile(const uint8_t *__restrict__ slo
   return P;
 }
 
+// The symbols of tile t into its zeroed LDS rows of ROW int16 from either index kind:
+// `index` the int64 tile index (3 words per tile), or (SLOTS) `six` the tile's records
+// of the close's index, which the caller loads ahead of its zero-fill.  Returns P, the
+// position after the tile's last symbol relative to the tile; pdc: the DC of the block
+// before the tile.  (Every AC position of the stream fits int32, and a carried run can
+// start far before the tile.)
+template <int ROW, bool SLOTS>
+__device__ __forceinline__ int tile_symbols(const uint8_t *__restrict__ sym_len, const int16_t *__restrict__ sym_val,
+                                            const int64_t *__restrict__ index, const SlotTileIx &six, int64_t t,
+                                            int rsh, int64_t nsym, int64_t ntiles, int span, int16_t *win, int trash,
+                                            int lane, int &pdc) {
+  if constexpr (SLOTS) {
+    pdc = six.r[0].z;
+    return slots_gather_tile<ROW>(sym_len, sym_val, six, t, rsh, span, win, trash, lane);
+  } else {
+    const int64_t o0 = index[3 * t] < nsym ? index[3 * t] : nsym;
+    const int64_t o1 = t + 1 < ntiles ? (index[3 * (t + 1)] < nsym ? index[3 * (t + 1)] : nsym) : nsym;
+    pdc = (int)index[3 * t + 2];
+    return gather_tile<ROW, HIC_DEC_G, HIC_DEC_PF>(sym_len, sym_val, o0, o1, nsym,
+                                                   (int)(index[3 * t + 1] + 1 - t * 64 * 63), span, win, trash, lane);
+  }
+}
+
+// *d_status of a whole stream, from the wave of its last tile (first AC position tb0,
+// P from tile_symbols): codec.decode_run_length's length, where an EOB zero-fills to the
+// end; -1 for a failed encode's count.  (A slot-layout stream is whole by construction:
+// its EOB zero-fills the rest.)
+template <bool SLOTS>
+__device__ __forceinline__ int64_t stream_status(int64_t nsym_raw, int64_t nsym, const uint8_t *__restrict__ sym_len,
+                                                 const int16_t *__restrict__ sym_val, int64_t tb0, int P,
+                                                 int64_t nblk) {
+  const int64_t total = tb0 + (int64_t)P, n_ac = nblk * 63;
+  const bool eob = SLOTS || (nsym > 0 && sym_len[nsym - 1] == 0 && sym_val[nsym - 1] == 0);
+  return nsym_raw < 1 ? -1 : ((eob && (SLOTS || total <= n_ac)) ? n_ac : total);
+}
+
 }  // namespace
 }  // namespace hic

@@ -141,11 +141,18 @@ def test_batch_table_reuse_and_rebuild(n, H, W, kind):
     _assert_batch(dec, [_decode_one(e) for e in sep], "tuples")
 
 
-@pytest.mark.parametrize("n,H,W,kind", [(3, 80, 1024, SLOTS), (3, 48, 80, INDEXED)])
+@pytest.mark.parametrize("n,H,W,kind", [
+    (3, 80, 1024, SLOTS),
+    (3, 48, 80, INDEXED),
+    (2, 96, 1040, INDEXED),  # tiles that wrap block rows, a partial last tile
+    (1, 16, 512, SLOTS),     # chroma is one half tile: dead lanes in the RGB form
+])
 def test_batch_equals_oracle_inverse_chain(n, H, W, kind):
     """Independent of the project's own decoder: the C oracle's dequantize + IDCT, pyrUp
-    and YCrCb -> RGB of each image's blocks."""
-    _, src, _ = _encoded(n, H, W, kind)
+    and YCrCb -> RGB of each image's blocks.  Image 0 from a one-image Decoder against
+    the same: the batch and the one-image kernels run one tile body, so their equality
+    alone does not check it."""
+    _, src, refs = _encoded(n, H, W, kind)
     dec = pipeline.BatchDecoder(n, H, W)
     got = dec.decode(src).cpu().numpy()
     dec.check_status()
@@ -159,6 +166,8 @@ def test_batch_equals_oracle_inverse_chain(n, H, W, kind):
             planes[k] = orcc.inv_dct_channel(raster, t)
         exp = orcc.ycrcb_to_rgb(planes["lum"], orcc.pyr_up(planes["cr"]), orcc.pyr_up(planes["cb"]))
         np.testing.assert_array_equal(got[i], exp, err_msg="image %d" % i)
+        if i == 0:
+            np.testing.assert_array_equal(refs[0][0], exp, err_msg="one-image Decoder, image 0")
 
 
 @pytest.mark.parametrize("n,H,W,kind", [(3, 80, 1024, SLOTS), (3, 48, 80, INDEXED)])

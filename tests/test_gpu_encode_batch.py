@@ -71,22 +71,31 @@ def test_batch_equals_per_image_encoder(n, H, W):
     assert [h.byte_stream() for h in batch.hic_images()] == [r["bytes"] for r in refs]
 
 
-def test_batch_equals_c_oracle():
-    """Independent of the one-image kernel: (3, 80, 1024) against the C oracle."""
-    n, H, W = 3, 80, 1024
+@pytest.mark.parametrize("n,H,W", [(3, 80, 1024), (2, 4112, 512)])
+def test_batch_equals_c_oracle(n, H, W):
+    """Independent of the project's own kernels: every image of the batch against the C
+    oracle, and image 0 from a one-image Encoder(H, W) against it too -- the batch's
+    close and the one-image close run one scan body, so their equality alone does not
+    check it.  (2, 4112, 512): 257 Y records, two scan partitions per Y channel, the
+    smallest shape whose close crosses the granule hand-off."""
     imgs = _images(n, H, W)
     batch = pipeline.BatchEncoder(n, H, W)
     batch.encode(device.to_device(imgs))
+    one = pipeline.Encoder(H, W)
+    assert one.slots
+    one.encode(device.to_device(imgs[0]))
     for i in range(n):
-        got = batch[i].result()
+        results = [("batch", batch[i].result())] + ([("one-image", one.result())] if i == 0 else [])
         y, cr, cb = orcc.rgb_to_ycrcb(imgs[i])
         for k, (p, t) in {"lum": (y, 0), "cr": (orcc.pyr_down(cr), 1), "cb": (orcc.pyr_down(cb), 1)}.items():
             zz = orcc.zigzag_blocks(orcc.dct_channel(p, t), 8)
             L, V = orcc.rle_encode(zz[:, 1:].reshape(-1), 15)
-            assert np.array_equal(got[k][0].astype(np.int32), zz), (i, k)
-            assert np.array_equal(got[k][1], orcc.dpcm(zz[:, 0].copy())), (i, k)
-            assert np.array_equal(got[k][2].astype(np.int32), L), (i, k)
-            assert np.array_equal(got[k][3].astype(np.int32), V), (i, k)
+            dc = orcc.dpcm(zz[:, 0].copy())
+            for who, got in results:
+                assert np.array_equal(got[k][0].astype(np.int32), zz), (who, i, k)
+                assert np.array_equal(got[k][1], dc), (who, i, k)
+                assert np.array_equal(got[k][2].astype(np.int32), L), (who, i, k)
+                assert np.array_equal(got[k][3].astype(np.int32), V), (who, i, k)
 
 
 @pytest.mark.parametrize("knob,value", [("encode_band", 0), ("encode_band", 1), ("encode_order", 0),

@@ -4,13 +4,15 @@ bodies of every kernel whose name contains SUBSTR in two device assembly listing
 
     hipcc --offload-arch=gfx950 <the Makefile's flags> --cuda-device-only -S file.hip -o listing.s
 
-of the same source file at two commits.  Kernels are matched by their leading
-template arguments (a new trailing template parameter renames every instantiation;
---new-suffix picks the instantiations of the new listing that stand for the old
-ones, e.g. 'Lb0E' for a new bool parameter that is false).  Symbol names are
+of the same source file at two commits.  Kernels are matched by name and leading
+template arguments, a kernel without template arguments on either side by its name
+alone (a new trailing template parameter renames every instantiation; --new-suffix
+picks the instantiations of the new listing that stand for the old ones, e.g. 'Lb0E'
+for a new bool parameter that is false).  Symbol names are
 normalised before comparing, so only instructions, labels and directives inside
 the bodies count.  Also prints each kernel's VGPRs, SGPRs, scratch and kernarg
-bytes.  Exit status 1 when a body differs or a kernel has no counterpart."""
+bytes, and its instruction count.  Exit status 1 when a body differs or a kernel has
+no counterpart."""
 import argparse
 import re
 import sys
@@ -41,9 +43,24 @@ def resources(path, sub):
     return res
 
 
-def targs(name, sub):
-    """The template-argument string that follows the kernel's name in the mangling."""
-    return name.split(sub, 1)[1]
+def ninstr(body):
+    return sum(1 for x in body if x.startswith("\t") and not x.startswith(("\t.", "\t;")))
+
+
+def key(name, sub):
+    """(the kernel's own name, its leading template arguments or '' without any) from
+    the mangling: SUBSTR may match several kernels (k_rle_scan: k_rle_scan16b<..>,
+    k_rle_scan_fold), with or without template arguments."""
+    for m in re.finditer(r"\d+", name):
+        for i in range(m.start(), m.end()):  # 'N_118k_x': the length is a suffix of the digits
+            n = int(name[i:m.end()])
+            ident = name[m.end():m.end() + n]
+            if len(ident) == n and sub in ident and name[m.end() + n:m.end() + n + 1] in ("I", "E"):
+                rest = name[m.end() + n:]
+                t = re.match(r"I((?:L[a-z]\d+E)+)", rest)
+                # (type arguments: the rest of the mangling tells the instantiations apart)
+                return ident, t.group(1) if t else (rest if rest.startswith("I") else "")
+    return name, ""
 
 
 def main():
@@ -55,24 +72,27 @@ def main():
     a = ap.parse_args()
     old, new = bodies(a.old, a.substr), bodies(a.new, a.substr)
     r_old, r_new = resources(a.old, a.substr), resources(a.new, a.substr)
+    show = lambda k: k[0] + ("<%s>" % k[1] if k[1] else "")  # noqa: E731
     bad = 0
     matched = set()
     for name in old:
-        lead = re.match(r"I((?:L[a-z]\d+E)+)", targs(name, a.substr)).group(1)
-        cand = [n for n in new if targs(n, a.substr).startswith("I" + lead + a.new_suffix)
-                and re.match(r"I((?:L[a-z]\d+E)+)", targs(n, a.substr)).group(1) == lead + a.new_suffix]
+        base, lead = key(name, a.substr)
+        # a kernel without template arguments on either side is matched by its name alone
+        cand = [n for n in new if key(n, a.substr)[0] == base
+                and (not lead or not key(n, a.substr)[1] or key(n, a.substr)[1] == lead + a.new_suffix)]
         if len(cand) != 1:
-            print("%s: %d counterparts" % (lead, len(cand)))
+            print("%s: %d counterparts; old %s" % (show((base, lead)), len(cand), r_old.get(name)))
             bad += 1
             continue
         matched.add(cand[0])
         same = old[name] == new[cand[0]]
         bad += not same
-        print("%s: %s (%d lines); old %s; new %s" % (lead, "identical" if same else "DIFFERENT", len(old[name]),
-                                                     r_old.get(name), r_new.get(cand[0])))
+        print("%s: %s (%d -> %d instructions); old %s; new %s" % (
+            show((base, lead)), "identical" if same else "DIFFERENT", ninstr(old[name]), ninstr(new[cand[0]]),
+            r_old.get(name), r_new.get(cand[0])))
     for n in new:
         if n not in matched:
-            print("new only %s: %s" % (re.match(r"I((?:L[a-z]\d+E)+)", targs(n, a.substr)).group(1), r_new.get(n)))
+            print("new only %s: %s" % (show(key(n, a.substr)), r_new.get(n)))
     sys.exit(1 if bad else 0)
 
 
