@@ -1033,7 +1033,6 @@ extern "C" int hic_encode420_u8(const uint8_t *rgb_rows, int64_t in_row0, int64_
 extern "C" int hic_encode420_batch_u8(int n, const hic_encode420_job *jobs, int max_len, void *stream,
                                      void *ev_start, void *ev_stop) {
   if (n < 1 || n > kEncBatchMax || !jobs) return arg_error("1 <= n <= %d jobs", kEncBatchMax);
-  if (max_len != 15 && max_len != 0) return arg_error("max_len 15 or 0");
   Enc420Batch B{};
   B.n = n;
   B.unit0[0] = 0;

@@ -183,8 +183,9 @@ int hic_encode420_seg_u8(const uint8_t *rgb_rows, int64_t in_row0, int64_t in_ro
 /* hic_encode420_batch_u8: n <= 8 hic_encode420_u8 calls in ONE launch (the row
  * shards of a multi-GPU group, one per image: a shard alone fills a sixth of the chip
  * at N = 8).  Each job as hic_encode420_u8's arguments; with workspaces, W % 512 == 0
- * (the records come from the kernel).  Every job is checked before the launch; the
- * events (nullable) time the whole launch. */
+ * (the records come from the kernel) and max_len 0..256 as hic_encode420_u8 takes
+ * it, one value for all jobs.  Every job is checked before the launch; the events
+ * (nullable) time the whole launch. */
 typedef struct {
   const uint8_t *rgb_rows;
   int64_t in_row0, in_rows, H, W, out_row0, out_rows;

@@ -102,6 +102,12 @@ def test_round6_batch_entry_points_refuse_bad_jobs():
     ragged = _lib.Encode420Job(p, 0, 64, 64, 768, 0, 64, p, p, p, p, p, p)  # records need a tile pass
     assert lib.hic_encode420_batch_u8(1, (_lib.Encode420Job * 1)(ragged), 15, None, None, None) == _lib.HIC_ERR_ARG
     assert "512" in _lib.last_error()
+    # max_len: what hic_encode420_u8 takes (0..256) for a job with workspaces, nothing outside it
+    for bad_len in (-1, 257):
+        assert lib.hic_encode420_batch_u8(1, (_lib.Encode420Job * 1)(job), bad_len, None, None, None) == _lib.HIC_ERR_ARG
+        assert "max_len" in _lib.last_error()
+        assert lib.hic_encode420_batch_u8(2, (_lib.Encode420Job * 2)(job, job), bad_len, None, None, None) \
+            == _lib.HIC_ERR_ARG
     # wire batches: a bad table, a null wire buffer, records without a destination, too many jobs
     w = _lib.WireJob(p, p, 64, 0, p, None, 0, 0, None, None)
     for badw in (_lib.WireJob(p, p, 64, 2, p, None, 0, 0, None, None), _lib.WireJob(p, None, 64, 0, p, None, 0, 0, None, None),
