@@ -43,6 +43,11 @@ class SlotJob(ctypes.Structure):
                 ("sym_val", _vp), ("sym_cap", _i64)]
 
 
+class KeyStream(ctypes.Structure):
+    """hic_key_stream (include/hiccup_hip.h): one int32 key stream of hic_huffman_batch_*."""
+    _fields_ = [("keys", _vp), ("n", _i64)]
+
+
 class WireJob(ctypes.Structure):
     """hic_wire_job (include/hiccup_hip.h): one segment of a batched wire pack / unpack."""
     _fields_ = [("blocks", _vp), ("wire", _vp), ("nblk", _i64), ("table_id", ctypes.c_int32), ("d_flag", _vp),
@@ -159,6 +164,13 @@ SIGNATURES = {
     "hic_slot_key_histogram": (_int, [_int, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "hic_slot_huffman_pack_workspace_bytes": (_sz, [_int, _vp]),
     "hic_slot_huffman_pack": (_int, [_int, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "hic_huffman_batch_key_range_workspace_bytes": (_sz, [_int]),
+    "hic_huffman_batch_key_range": (_int, [_int, _vp, _vp, _int, _vp, _vp, _sz, _vp]),
+    "hic_huffman_batch_histogram_workspace_bytes": (_sz, [_int, _vp, _vp, _vp]),
+    "hic_huffman_batch_histogram": (_int, [_int, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "hic_huffman_batch_pack_workspace_bytes": (_sz, [_int, _vp, _vp]),
+    "hic_huffman_batch_pack": (_int, [_int, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "hic_huffman_build_batch": (_int, [_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "hic_rle_decode_i16_slots": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _vp, _vp, _vp, _vp]),
     "hic_rle_decode_idct_u8_slots": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _i64, _i64, _int, _vp, _i64, _vp, _vp]),
     "hic_rle_decode_idct_u8_slots_pair": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _i64, _i64, _int, _vp, _i64, _vp,

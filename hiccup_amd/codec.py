@@ -471,8 +471,9 @@ def encode_batch(images):
     tensors, or one stacked (n, H, W, 3) array or tensor -> [HicImage], each byte for
     byte encode(image).  Host input goes up in one copy; the n images are encoded by
     one fused launch and closed by one scan launch (pipeline.BatchEncoder), then the
-    Huffman stage runs per image (its nine trees per image stay on the host).  A shape
-    the batch refuses, or mixed shapes, goes through encode per image."""
+    Huffman stage takes all 9 n streams in one pass per phase (huffman.BatchStreams;
+    pipeline.batched_default says for which batches).  A shape the batch refuses, or
+    mixed shapes, goes through encode per image."""
     with _gc_paused():
         return _encode_batch(images)
 

@@ -23,6 +23,15 @@
 //                     the same three steps over channels still in the slot layout
 //                     (slots.h), every channel in one grid per phase and no compaction
 //                     (the second half of this file)
+//  hic_huffman_batch_key_range / _histogram / _pack
+//                     the same three steps over the 9 n streams of n slot-layout
+//                     images, one call per phase: the jobs in a table in device
+//                     memory, the kernel bodies those of the entry points above
+//                     (the end of this file)
+#include <string.h>
+
+#include <vector>
+
 #include "hic_common.h"
 
 namespace hic {
@@ -43,10 +52,12 @@ __device__ __forceinline__ int key_at(const void *keys, int kb, int64_t i) {
 // min / max of the keys; keys at a 16-byte aligned address are read 16 bytes per
 // load (the 8K jpeg_encode's nine streams: ~105 us per large stream read one key per
 // load, 1- and 2-byte keys included)
+// (workgroup wg of the nwg that share the stream)
 template <int KB, bool VEC>
-__global__ __launch_bounds__(kHT) void k_key_range(const void *__restrict__ keys, int64_t n, int *__restrict__ mm) {
+__device__ __forceinline__ void key_range_body(const void *__restrict__ keys, int64_t n, int *__restrict__ mm, int wg,
+                                               int nwg) {
   int lo = 2147483647, hi = -2147483647 - 1;
-  const int64_t t0 = (int64_t)blockIdx.x * kHT + threadIdx.x, stride = (int64_t)gridDim.x * kHT;
+  const int64_t t0 = (int64_t)wg * kHT + threadIdx.x, stride = (int64_t)nwg * kHT;
   int64_t tail = 0;
   if constexpr (VEC) {
     constexpr int kPer = 16 / KB;  // keys per 16-byte load
@@ -105,16 +116,20 @@ __global__ __launch_bounds__(kHT) void k_key_range(const void *__restrict__ keys
     atomicMax(mm + 1, hi);
   }
 }
+template <int KB, bool VEC>
+__global__ __launch_bounds__(kHT) void k_key_range(const void *__restrict__ keys, int64_t n, int *__restrict__ mm) {
+  key_range_body<KB, VEC>(keys, n, mm, blockIdx.x, gridDim.x);
+}
 
 // counts / first: nbins entries, zero / 0xFFFFFFFF initialised by the launcher
 // LDS: privatised bins; with `part` each workgroup stores its bins (count, first) to
 // part[blockIdx.x] and k_hist_reduce sums them -- per-workgroup global atomics on
 // every bin (512 workgroups x thousands of bins) took ~55 us per large stream
-template <bool LDS>
-__global__ __launch_bounds__(kHT) void k_key_hist(const void *__restrict__ keys, int kb, int64_t n, int key_min,
-                                                  int nbins, uint32_t *__restrict__ counts,
-                                                  uint32_t *__restrict__ first, uint32_t *__restrict__ part = nullptr) {
-  __shared__ uint32_t s_cnt[LDS ? kHistLds : 1], s_first[LDS ? kHistLds : 1];
+// (LDS: whether s_cnt / s_first hold the bins; workgroup wg of the stream's nwg)
+__device__ __forceinline__ void key_hist_body(const bool LDS, uint32_t *s_cnt, uint32_t *s_first,
+                                              const void *__restrict__ keys, int kb, int64_t n, int key_min, int nbins,
+                                              uint32_t *__restrict__ counts, uint32_t *__restrict__ first,
+                                              uint32_t *__restrict__ part, int wg, int nwg) {
   if (LDS) {
     for (int b = threadIdx.x; b < nbins; b += kHT) {
       s_cnt[b] = 0;
@@ -122,7 +137,7 @@ __global__ __launch_bounds__(kHT) void k_key_hist(const void *__restrict__ keys,
     }
     __syncthreads();
   }
-  for (int64_t i = (int64_t)blockIdx.x * kHT + threadIdx.x; i < n; i += (int64_t)gridDim.x * kHT) {
+  for (int64_t i = (int64_t)wg * kHT + threadIdx.x; i < n; i += (int64_t)nwg * kHT) {
     const int b = key_at(keys, kb, i) - key_min;
     if ((unsigned)b >= (unsigned)nbins) continue;  // outside the caller's range: not counted
     if (LDS) {
@@ -138,7 +153,7 @@ __global__ __launch_bounds__(kHT) void k_key_hist(const void *__restrict__ keys,
   if (LDS) {
     __syncthreads();
     if (part) {
-      uint32_t *pc = part + (int64_t)blockIdx.x * 2 * nbins;
+      uint32_t *pc = part + (int64_t)wg * 2 * nbins;
       for (int b = threadIdx.x; b < nbins; b += kHT) {
         pc[b] = s_cnt[b];
         pc[nbins + b] = s_first[b];
@@ -153,10 +168,17 @@ __global__ __launch_bounds__(kHT) void k_key_hist(const void *__restrict__ keys,
     }
   }
 }
+template <bool LDS>
+__global__ __launch_bounds__(kHT) void k_key_hist(const void *__restrict__ keys, int kb, int64_t n, int key_min,
+                                                  int nbins, uint32_t *__restrict__ counts,
+                                                  uint32_t *__restrict__ first, uint32_t *__restrict__ part = nullptr) {
+  __shared__ uint32_t s_cnt[LDS ? kHistLds : 1], s_first[LDS ? kHistLds : 1];
+  key_hist_body(LDS, s_cnt, s_first, keys, kb, n, key_min, nbins, counts, first, part, blockIdx.x, gridDim.x);
+}
 
 // counts[b] / first[b] = the sum / min of the nwg workgroups' partial bins
-__global__ __launch_bounds__(kHT) void k_hist_reduce(const uint32_t *__restrict__ part, int nwg, int nbins,
-                                                     uint32_t *__restrict__ counts, uint32_t *__restrict__ first) {
+__device__ __forceinline__ void hist_reduce_body(const uint32_t *__restrict__ part, int nwg, int nbins,
+                                                 uint32_t *__restrict__ counts, uint32_t *__restrict__ first) {
   const int b = blockIdx.x * kHT + threadIdx.x;
   if (b >= nbins) return;
   uint32_t c = 0, f = 0xFFFFFFFFu;
@@ -167,6 +189,10 @@ __global__ __launch_bounds__(kHT) void k_hist_reduce(const uint32_t *__restrict_
   }
   counts[b] = c;
   first[b] = f;
+}
+__global__ __launch_bounds__(kHT) void k_hist_reduce(const uint32_t *__restrict__ part, int nwg, int nbins,
+                                                     uint32_t *__restrict__ counts, uint32_t *__restrict__ first) {
+  hist_reduce_body(part, nwg, nbins, counts, first);
 }
 
 // block-wide exclusive sum (256 threads = 4 waves)
@@ -192,9 +218,9 @@ __device__ __forceinline__ int64_t blk_excl_sum(int64_t v, int64_t *s_w, int64_t
 }
 
 // pass A: bits per tile
-__global__ __launch_bounds__(kHT) void k_pack_sizes(const void *__restrict__ keys, int kb, int64_t n, int key_min,
-                                                    int nbins, const uint8_t *__restrict__ code_len,
-                                                    int64_t *__restrict__ tile_bits) {
+__device__ __forceinline__ void pack_sizes_body(const void *__restrict__ keys, int kb, int64_t n, int key_min,
+                                                int nbins, const uint8_t *__restrict__ code_len,
+                                                int64_t *__restrict__ tile_bits) {
   __shared__ int64_t s_w[kHT / 64];
   const int64_t s0 = (int64_t)blockIdx.x * kHTile + (int64_t)threadIdx.x * kHPT;
   int64_t acc = 0;
@@ -207,6 +233,11 @@ __global__ __launch_bounds__(kHT) void k_pack_sizes(const void *__restrict__ key
   int64_t total;
   blk_excl_sum(acc, s_w, total);
   if (threadIdx.x == 0) tile_bits[blockIdx.x] = total;
+}
+__global__ __launch_bounds__(kHT) void k_pack_sizes(const void *__restrict__ keys, int kb, int64_t n, int key_min,
+                                                    int nbins, const uint8_t *__restrict__ code_len,
+                                                    int64_t *__restrict__ tile_bits) {
+  pack_sizes_body(keys, kb, n, key_min, nbins, code_len, tile_bits);
 }
 
 // in-place exclusive scan of n int64 by one workgroup; *total = the sum
@@ -279,12 +310,11 @@ __device__ __forceinline__ void pack_tile(const int (&ks)[kHPT], const uint64_t 
     }
   }
 }
-__global__ __launch_bounds__(kHT) void k_pack_bits(const void *__restrict__ keys, int kb, int64_t n, int key_min,
-                                                   int nbins, const uint64_t *__restrict__ code_bits,
-                                                   const uint8_t *__restrict__ code_len,
-                                                   const int64_t *__restrict__ tile_off, uint32_t *__restrict__ out,
-                                                   int64_t out_words) {
-  extern __shared__ uint32_t s_words[];
+__device__ __forceinline__ void pack_bits_body(const void *__restrict__ keys, int kb, int64_t n, int key_min,
+                                               int nbins, const uint64_t *__restrict__ code_bits,
+                                               const uint8_t *__restrict__ code_len,
+                                               const int64_t *__restrict__ tile_off, uint32_t *__restrict__ out,
+                                               int64_t out_words, uint32_t *s_words) {
   __shared__ int64_t s_w[kHT / 64];
   const int64_t s0 = (int64_t)blockIdx.x * kHTile + (int64_t)threadIdx.x * kHPT;
   int ks[kHPT];
@@ -294,6 +324,69 @@ __global__ __launch_bounds__(kHT) void k_pack_bits(const void *__restrict__ keys
     if ((unsigned)ks[k] >= (unsigned)nbins) ks[k] = -1;
   }
   pack_tile(ks, code_bits, code_len, tile_off[blockIdx.x], out, out_words, s_words, s_w);
+}
+__global__ __launch_bounds__(kHT) void k_pack_bits(const void *__restrict__ keys, int kb, int64_t n, int key_min,
+                                                   int nbins, const uint64_t *__restrict__ code_bits,
+                                                   const uint8_t *__restrict__ code_len,
+                                                   const int64_t *__restrict__ tile_off, uint32_t *__restrict__ out,
+                                                   int64_t out_words) {
+  extern __shared__ uint32_t s_words[];
+  pack_bits_body(keys, kb, n, key_min, nbins, code_bits, code_len, tile_off, out, out_words, s_words);
+}
+
+// The batched forms of the five kernels above (hic_huffman_batch_*): blockIdx.y = the
+// stream, an int32 key stream (a DC stream) whose job is read from a table in device
+// memory as the slot kernels' HsTable reads theirs; the bodies are the ones above.
+// The grid's x is sized for the batch's longest stream: workgroups past a stream's
+// own count leave at once, and the job's n bounds every load.
+struct HkJob {
+  const int32_t *keys;
+  int64_t n;
+  int key_min, nbins;
+  uint32_t *cnt, *first;
+  uint32_t *part;   // histogram: [nwg][2][nbins] per-workgroup bins; null: straight into cnt / first
+  int nwg;          // histogram: the stream's workgroups
+  int nt;           // pack: the stream's tiles
+  const uint64_t *cbits;
+  const uint8_t *clen;
+  uint32_t *out;
+  int64_t out_words;
+  int64_t *tile;    // [nt]: the tiles' bits, then their first bits
+  int64_t *d_nbits;
+};
+typedef const __attribute__((address_space(4))) HkJob HkJobC;
+__device__ __forceinline__ HkJobC &hk_job(const HkJob *tab) { return *(HkJobC *)(uintptr_t)(tab + blockIdx.y); }
+
+__global__ __launch_bounds__(kHT) void k_key_range_table(const HkJob *tab, int *__restrict__ mm) {
+  HkJobC &J = hk_job(tab);
+  key_range_body<4, true>(J.keys, J.n, mm + 2 * blockIdx.y, blockIdx.x, gridDim.x);
+}
+__global__ __launch_bounds__(kHT) void k_key_hist_table(const HkJob *tab) {
+  __shared__ uint32_t s_cnt[kHistLds], s_first[kHistLds];
+  HkJobC &J = hk_job(tab);
+  if ((int)blockIdx.x >= J.nwg) return;
+  key_hist_body(J.nbins <= kHistLds, s_cnt, s_first, J.keys, 4, J.n, J.key_min, J.nbins, J.cnt, J.first, J.part,
+                blockIdx.x, J.nwg);
+}
+__global__ __launch_bounds__(kHT) void k_hist_reduce_table(const HkJob *tab) {
+  HkJobC &J = hk_job(tab);
+  if (!J.part) return;
+  hist_reduce_body(J.part, J.nwg, J.nbins, J.cnt, J.first);
+}
+__global__ __launch_bounds__(kHT) void k_pack_sizes_table(const HkJob *tab) {
+  HkJobC &J = hk_job(tab);
+  if ((int)blockIdx.x >= J.nt) return;
+  pack_sizes_body(J.keys, 4, J.n, J.key_min, J.nbins, J.clen, J.tile);
+}
+__global__ __launch_bounds__(kHT) void k_pack_scan_table(const HkJob *tab) {
+  HkJobC &J = hk_job(tab);
+  scan_in_place(J.tile, J.nt, J.d_nbits);
+}
+__global__ __launch_bounds__(kHT) void k_pack_bits_table(const HkJob *tab) {
+  extern __shared__ uint32_t s_words[];
+  HkJobC &J = hk_job(tab);
+  if ((int)blockIdx.x >= J.nt) return;
+  pack_bits_body(J.keys, 4, J.n, J.key_min, J.nbins, J.cbits, J.clen, J.tile, J.out, J.out_words, s_words);
 }
 
 // ---------------------------------------------------------------------------
@@ -324,14 +417,28 @@ struct HsJob {
   int64_t *bits[2];        // per record: its bit size (pass A), then its first bit (the scan)
   int64_t *d_nbits;        // [2]
 };
+// Where a kernel's job comes from (its template parameter Src; blockIdx.y = the
+// channel): one image's up to three jobs by value in the kernel arguments, or a
+// batch's 3 n jobs in a table in device memory (hic_huffman_batch_*).  The table
+// is complete before the launch and is read through a constant-address-space
+// reference: the workgroup-uniform reads become scalar loads, and the pointers
+// they yield are known to be global ones.  The kernel bodies are the same.
 struct HsJobs {
   HsJob j[3];
   int n, M;
+  __device__ const HsJob &job(int y) const { return j[y]; }
+};
+typedef const __attribute__((address_space(4))) HsJob HsJobC;
+struct HsTable {
+  const HsJob *tab;
+  int M;
+  __device__ HsJobC &job(int y) const { return *(HsJobC *)(uintptr_t)(tab + y); }
 };
 static_assert(kSlotCapMax <= kHTile, "a slot fits one pack tile");
 
 // record r: its slot symbols n, those plus the EOB ne, its fillers and stream offset
-__device__ __forceinline__ void hs_record(const HsJob &J, int64_t r, int &n, int &ne, int &nf, int64_t &off) {
+template <class JT>
+__device__ __forceinline__ void hs_record(JT &J, int64_t r, int &n, int &ne, int &nf, int64_t &off) {
   const int4 ix = *reinterpret_cast<const int4 *>(J.sidx + 4 * r);
   n = ix.x;
   nf = ix.w;
@@ -341,8 +448,8 @@ __device__ __forceinline__ void hs_record(const HsJob &J, int64_t r, int &n, int
 
 // the keys of symbols 16 c .. 16 c + 15 of record r in stream S (16-byte loads; the
 // EOB's key is 0); returns how many of them exist (0..16)
-template <int S>
-__device__ __forceinline__ int hs_keys16(const HsJob &J, int64_t r, int c, int n, int ne, int (&key)[16]) {
+template <int S, class JT>
+__device__ __forceinline__ int hs_keys16(JT &J, int64_t r, int c, int n, int ne, int (&key)[16]) {
   const int m = ne - 16 * c < 16 ? ne - 16 * c : 16;
   if (m <= 0) return 0;
   if (S == 0) {
@@ -364,9 +471,10 @@ __device__ __forceinline__ int hs_keys16(const HsJob &J, int64_t r, int c, int n
 }
 
 // d_minmax[4 y .. 4 y + 3] = channel y's {min, max} of the lengths, of the values
-__global__ __launch_bounds__(kHT) void k_slot_range(HsJobs jobs, int *__restrict__ mm) {
+template <class Src>
+__global__ __launch_bounds__(kHT) void k_slot_range(Src jobs, int *__restrict__ mm) {
   __shared__ int s_r[4][kHT / 64];
-  const HsJob &J = jobs.j[blockIdx.y];
+  auto &J = jobs.job(blockIdx.y);
   const int64_t a = J.nrec * blockIdx.x / gridDim.x, b = J.nrec * (blockIdx.x + 1) / gridDim.x;
   int v[4] = {2147483647, -2147483647 - 1, 2147483647, -2147483647 - 1};
   auto see = [&](int s, int k) {
@@ -418,9 +526,10 @@ __global__ __launch_bounds__(kHT) void k_slot_range(HsJobs jobs, int *__restrict
 // channel's lengths then its values, <= kHistLds together) stored per workgroup to J.part for
 // k_slot_hist_reduce, as k_key_hist does; a channel whose bins exceed the LDS
 // (J.part null) adds into the zero / 0xFFFFFFFF initialised outputs.
-__global__ __launch_bounds__(kHT) void k_slot_hist(HsJobs jobs) {
+template <class Src>
+__global__ __launch_bounds__(kHT) void k_slot_hist(Src jobs) {
   __shared__ uint32_t s_cnt[kHistLds], s_first[kHistLds];
-  const HsJob &J = jobs.j[blockIdx.y];
+  auto &J = jobs.job(blockIdx.y);
   const bool lds = J.part != nullptr;
   const int nb0 = J.nbins[0], nbt = nb0 + J.nbins[1];
   if (lds) {
@@ -475,8 +584,9 @@ __global__ __launch_bounds__(kHT) void k_slot_hist(HsJobs jobs) {
 }
 
 // the sum / min of a channel's nwg partial bins into its two streams' outputs
-__global__ __launch_bounds__(kHT) void k_slot_hist_reduce(HsJobs jobs, int nwg) {
-  const HsJob &J = jobs.j[blockIdx.y];
+template <class Src>
+__global__ __launch_bounds__(kHT) void k_slot_hist_reduce(Src jobs, int nwg) {
+  auto &J = jobs.job(blockIdx.y);
   const int nb0 = J.nbins[0], nbt = nb0 + J.nbins[1];
   const int b = blockIdx.x * kHT + threadIdx.x;
   if (!J.part || b >= nbt) return;
@@ -492,7 +602,8 @@ __global__ __launch_bounds__(kHT) void k_slot_hist_reduce(HsJobs jobs, int nwg) 
 }
 
 // a stream's filler code: (length, bits) of key `key`; length 0 outside the table
-__device__ __forceinline__ int hs_fill_code(const HsJob &J, int s, int key, uint64_t &bits) {
+template <class JT>
+__device__ __forceinline__ int hs_fill_code(JT &J, int s, int key, uint64_t &bits) {
   const int b = key - J.key_min[s];
   if ((unsigned)b >= (unsigned)J.nbins[s]) return 0;
   bits = J.cbits[s][b];
@@ -500,8 +611,8 @@ __device__ __forceinline__ int hs_fill_code(const HsJob &J, int s, int key, uint
 }
 
 // the 16 table indices (-1: codes to nothing) of thread t's symbols of record r
-template <int S>
-__device__ __forceinline__ void hs_index16(const HsJob &J, int64_t r, int n, int ne, int (&ks)[kHPT]) {
+template <int S, class JT>
+__device__ __forceinline__ void hs_index16(JT &J, int64_t r, int n, int ne, int (&ks)[kHPT]) {
   static_assert(kHPT == 16, "one 16-byte chunk of lengths per thread");
   const int m = hs_keys16<S>(J, r, threadIdx.x, n, ne, ks);
 #pragma unroll
@@ -512,9 +623,10 @@ __device__ __forceinline__ void hs_index16(const HsJob &J, int64_t r, int n, int
 }
 
 // pack pass A: one workgroup per record: the bits of its fillers + its symbols, both streams
-__global__ __launch_bounds__(kHT) void k_slot_pack_sizes(HsJobs jobs) {
+template <class Src>
+__global__ __launch_bounds__(kHT) void k_slot_pack_sizes(Src jobs) {
   __shared__ int64_t s_w[kHT / 64];
-  const HsJob &J = jobs.j[blockIdx.y];
+  auto &J = jobs.job(blockIdx.y);
   const int64_t r = blockIdx.x;
   if (r >= J.nrec) return;
   int n, ne, nf;
@@ -538,17 +650,19 @@ __global__ __launch_bounds__(kHT) void k_slot_pack_sizes(HsJobs jobs) {
 }
 
 // the records' first bits: one workgroup per stream
-__global__ __launch_bounds__(kHT) void k_slot_pack_scan(HsJobs jobs) {
-  const HsJob &J = jobs.j[blockIdx.y];
+template <class Src>
+__global__ __launch_bounds__(kHT) void k_slot_pack_scan(Src jobs) {
+  auto &J = jobs.job(blockIdx.y);
   scan_in_place(J.bits[blockIdx.x], J.nrec, J.d_nbits + blockIdx.x);
 }
 
 // pack pass B: one workgroup per record packs its slot's symbols (after its fillers'
 // bits, which k_slot_pack_fill writes) as one tile of each stream
-__global__ __launch_bounds__(kHT) void k_slot_pack_bits(HsJobs jobs) {
+template <class Src>
+__global__ __launch_bounds__(kHT) void k_slot_pack_bits(Src jobs) {
   extern __shared__ uint32_t s_words[];
   __shared__ int64_t s_w[kHT / 64];
-  const HsJob &J = jobs.j[blockIdx.y];
+  auto &J = jobs.job(blockIdx.y);
   const int64_t r = blockIdx.x;
   if (r >= J.nrec) return;
   int n, ne, nf;
@@ -597,10 +711,11 @@ __device__ __forceinline__ void hs_fill_word(uint32_t *__restrict__ out, int64_t
 // batch's own workgroup (batches dealt round-robin), a long one -- a carried zero run
 // can span nearly the whole channel -- word by word by ALL the channel's workgroups.
 constexpr int kFillShort = 16;
-__global__ __launch_bounds__(kHT) void k_slot_pack_fill(HsJobs jobs) {
+template <class Src>
+__global__ __launch_bounds__(kHT) void k_slot_pack_fill(Src jobs) {
   __shared__ int s_list[2 * kHT];
   __shared__ int s_nlist;
-  const HsJob &J = jobs.j[blockIdx.y];
+  auto &J = jobs.job(blockIdx.y);
   uint64_t fc[2] = {0, 0};
   const int fl[2] = {hs_fill_code(J, 0, jobs.M - 1, fc[0]), hs_fill_code(J, 1, 0, fc[1])};
   if (fl[0] == 0 && fl[1] == 0) return;  // no filler in the tables: no run
@@ -727,6 +842,7 @@ extern "C" int hic_huffman_pack(const void *keys, int key_bytes, int64_t n, int3
 
 // ---- the slot layout's streams (the kernels' comment above) ----
 // hic_slot_job[n] -> the kernels' jobs; everything is checked before any device call
+static int hs_job_one(int k, const hic_slot_job &a, HsJob &j);
 static int hs_jobs(int n, const hic_slot_job *jobs, int max_len, HsJobs &J, int64_t &max_nrec) {
   if (n < 1 || n > 3 || !jobs) return arg_error("1 <= n <= 3 jobs");
   if (max_len != 15) return arg_error("the slot layout needs max_len 15");
@@ -735,28 +851,31 @@ static int hs_jobs(int n, const hic_slot_job *jobs, int max_len, HsJobs &J, int6
   J.M = max_len;
   max_nrec = 0;
   for (int k = 0; k < n; ++k) {
-    const hic_slot_job &a = jobs[k];
-    if (!a.slot_len || !a.slot_val || !a.d_index || !a.workspace || !a.d_count) return arg_error("job %d: null pointer", k);
-    // (a stream holds at most nblk * 63 + 1 symbols: positions fit 32 bits)
-    if (a.nblk <= 0 || a.nblk > (int64_t)INT32_MAX / 63) return arg_error("job %d: nblk", k);
-    if (a.records_per_tile != 1 && a.records_per_tile != 2) return arg_error("job %d: records_per_tile must be 1 or 2", k);
-    const int64_t bpr = 64 / a.records_per_tile;
-    if (a.nblk % bpr) return arg_error("job %d: nblk must be a multiple of %lld (whole records)", k, (long long)bpr);
-    if ((reinterpret_cast<uintptr_t>(a.slot_len) | reinterpret_cast<uintptr_t>(a.slot_val) |
-         reinterpret_cast<uintptr_t>(a.d_index)) % 16)
-      return arg_error("job %d: slot arrays and index must be 16-byte aligned", k);
-    if (a.workspace_bytes < (int64_t)hic_rle_slots_workspace_bytes(a.nblk, (int)a.records_per_tile))
-      return arg_error("job %d: workspace too small", k);
-    HsJob &j = J.j[k];
-    j.slot_len = a.slot_len;
-    j.slot_val = a.slot_val;
-    j.sidx = a.d_index;
-    j.nrec = slot_nrec(a.nblk, a.records_per_tile);
-    j.offs = static_cast<const int64_t *>(a.workspace) + rle_offs_word(j.nrec);
-    j.d_count = a.d_count;
-    j.capr = (int)(63 * bpr);
-    max_nrec = j.nrec > max_nrec ? j.nrec : max_nrec;
+    if (int e = hs_job_one(k, jobs[k], J.j[k])) return e;
+    max_nrec = J.j[k].nrec > max_nrec ? J.j[k].nrec : max_nrec;
   }
+  return HIC_OK;
+}
+// job k of an entry point: its checks, and the fields every phase reads
+static int hs_job_one(int k, const hic_slot_job &a, HsJob &j) {
+  if (!a.slot_len || !a.slot_val || !a.d_index || !a.workspace || !a.d_count) return arg_error("job %d: null pointer", k);
+  // (a stream holds at most nblk * 63 + 1 symbols: positions fit 32 bits)
+  if (a.nblk <= 0 || a.nblk > (int64_t)INT32_MAX / 63) return arg_error("job %d: nblk", k);
+  if (a.records_per_tile != 1 && a.records_per_tile != 2) return arg_error("job %d: records_per_tile must be 1 or 2", k);
+  const int64_t bpr = 64 / a.records_per_tile;
+  if (a.nblk % bpr) return arg_error("job %d: nblk must be a multiple of %lld (whole records)", k, (long long)bpr);
+  if ((reinterpret_cast<uintptr_t>(a.slot_len) | reinterpret_cast<uintptr_t>(a.slot_val) |
+       reinterpret_cast<uintptr_t>(a.d_index)) % 16)
+    return arg_error("job %d: slot arrays and index must be 16-byte aligned", k);
+  if (a.workspace_bytes < (int64_t)hic_rle_slots_workspace_bytes(a.nblk, (int)a.records_per_tile))
+    return arg_error("job %d: workspace too small", k);
+  j.slot_len = a.slot_len;
+  j.slot_val = a.slot_val;
+  j.sidx = a.d_index;
+  j.nrec = slot_nrec(a.nblk, a.records_per_tile);
+  j.offs = static_cast<const int64_t *>(a.workspace) + rle_offs_word(j.nrec);
+  j.d_count = a.d_count;
+  j.capr = (int)(63 * bpr);
   return HIC_OK;
 }
 
@@ -791,7 +910,7 @@ extern "C" int hic_slot_key_range(int n, const hic_slot_job *jobs, int max_len, 
     return e;
   const int64_t want = (max_nrec + 7) / 8;
   const int grid = (int)(want < cu_count() ? want : cu_count());
-  hipLaunchKernelGGL(k_slot_range, dim3(grid, n), dim3(kHT), 0, s, J, d_minmax);
+  hipLaunchKernelGGL(k_slot_range<HsJobs>, dim3(grid, n), dim3(kHT), 0, s, J, d_minmax);
   return check_launch("k_slot_range");
 }
 
@@ -848,10 +967,10 @@ extern "C" int hic_slot_key_histogram(int n, const hic_slot_job *jobs, int max_l
       p += (int64_t)grid * 2 * nbt;
     }
   }
-  hipLaunchKernelGGL(k_slot_hist, dim3(grid, n), dim3(kHT), 0, s, J);
+  hipLaunchKernelGGL(k_slot_hist<HsJobs>, dim3(grid, n), dim3(kHT), 0, s, J);
   if (int e = check_launch("k_slot_hist")) return e;
   if (!words) return HIC_OK;
-  hipLaunchKernelGGL(k_slot_hist_reduce, dim3((unsigned)((max_nbt + kHT - 1) / kHT), n), dim3(kHT), 0, s, J, grid);
+  hipLaunchKernelGGL(k_slot_hist_reduce<HsJobs>, dim3((unsigned)((max_nbt + kHT - 1) / kHT), n), dim3(kHT), 0, s, J, grid);
   if (int e = check_launch("k_slot_hist_reduce")) return e;
   return hip_status(hipFreeAsync(part, s), "hipFreeAsync");
 }
@@ -888,11 +1007,292 @@ extern "C" int hic_slot_huffman_pack(int n, const hic_slot_job *jobs, int max_le
   }
   hipStream_t s = as_stream(stream);
   if (int e = memset_regions(2 * n, h_out, out_bytes, 0, s)) return e;
-  hipLaunchKernelGGL(k_slot_pack_sizes, dim3((unsigned)max_nrec, n), dim3(kHT), 0, s, J);
-  hipLaunchKernelGGL(k_slot_pack_scan, dim3(2, n), dim3(kHT), 0, s, J);
-  hipLaunchKernelGGL(k_slot_pack_bits, dim3((unsigned)max_nrec, n), dim3(kHT), kPackWords * sizeof(uint32_t), s, J);
+  hipLaunchKernelGGL(k_slot_pack_sizes<HsJobs>, dim3((unsigned)max_nrec, n), dim3(kHT), 0, s, J);
+  hipLaunchKernelGGL(k_slot_pack_scan<HsJobs>, dim3(2, n), dim3(kHT), 0, s, J);
+  hipLaunchKernelGGL(k_slot_pack_bits<HsJobs>, dim3((unsigned)max_nrec, n), dim3(kHT), kPackWords * sizeof(uint32_t), s, J);
   const int64_t batches = (max_nrec + kHT - 1) / kHT;
   const int fgrid = (int)(batches * 8 < cu_count() ? batches * 8 : cu_count());
-  hipLaunchKernelGGL(k_slot_pack_fill, dim3(fgrid, n), dim3(kHT), 0, s, J);
+  hipLaunchKernelGGL(k_slot_pack_fill<HsJobs>, dim3(fgrid, n), dim3(kHT), 0, s, J);
+  return check_launch("k_slot_pack_fill");
+}
+
+// ---- the batch's 9 n streams, one pass per phase (hic_huffman_batch_*) ----
+// Stream order of every per-stream array: the 3 n DC streams (image i's Y, Cr, Cb =
+// 3 i .. 3 i + 2), then the 6 n slot streams (channel c = 3 i + k gives 3 n + 2 c,
+// its lengths, and 3 n + 2 c + 1, its values).  Bins and outputs lie back to back in
+// that order, so one memset covers each kind.  The jobs of a phase are written into
+// two host tables, copied into the caller's workspace, and read there by the kernels.
+namespace {
+
+constexpr int kHbGrid = 256;  // the range / histogram grids' x per channel at most (an MI355X's compute units)
+
+struct HbPlan {
+  int n = 0;
+  std::vector<HsJob> sj;  // 3 n
+  std::vector<HkJob> kj;  // 3 n
+  int64_t max_nrec = 0, max_keys = 0;
+  int sgrid() const {  // workgroups per slot channel of the range and the histogram
+    const int64_t want = (max_nrec + 7) / 8;
+    return (int)(want < kHbGrid ? want : kHbGrid);
+  }
+};
+
+size_t hb_table_bytes(int n) {
+  return (size_t)(round_up(3 * (int64_t)n * sizeof(HsJob), 16) + round_up(3 * (int64_t)n * sizeof(HkJob), 16));
+}
+
+// every job checked, nothing launched
+int hb_plan(int n, const hic_slot_job *jobs, const hic_key_stream *dc, int max_len, HbPlan &P) {
+  if (n < 1 || n > HIC_SLOTS_BATCH_MAX) return arg_error("1 <= n <= HIC_SLOTS_BATCH_MAX images");
+  if (!jobs || !dc) return arg_error("null pointer");
+  if (max_len != 15) return arg_error("the slot layout needs max_len 15");
+  P.n = n;
+  P.sj.assign(3 * (size_t)n, HsJob{});
+  P.kj.assign(3 * (size_t)n, HkJob{});
+  for (int k = 0; k < 3 * n; ++k) {
+    if (int e = hs_job_one(k, jobs[k], P.sj[k])) return e;
+    P.max_nrec = P.sj[k].nrec > P.max_nrec ? P.sj[k].nrec : P.max_nrec;
+    if (!dc[k].keys) return arg_error("DC stream %d: null pointer", k);
+    if (reinterpret_cast<uintptr_t>(dc[k].keys) % 16) return arg_error("DC stream %d: keys must be 16-byte aligned", k);
+    if (dc[k].n <= 0 || dc[k].n > INT32_MAX) return arg_error("DC stream %d: n", k);
+    P.kj[k].keys = dc[k].keys;
+    P.kj[k].n = dc[k].n;
+    P.max_keys = dc[k].n > P.max_keys ? dc[k].n : P.max_keys;
+  }
+  // (a grid holds fewer than 2^32 threads)
+  const int64_t wide = P.max_nrec > (P.max_keys + kHTile - 1) / kHTile ? P.max_nrec : (P.max_keys + kHTile - 1) / kHTile;
+  if (wide * 3 * n > ((int64_t)1 << 32) / kHT - 1) return arg_error("the batch's records exceed one grid");
+  return HIC_OK;
+}
+
+int hb_bins(HbPlan &P, const int32_t *key_min, const int32_t *nbins, int64_t &total) {
+  if (!key_min || !nbins) return arg_error("null pointer");
+  const int m = 3 * P.n;
+  total = 0;
+  for (int i = 0; i < 9 * P.n; ++i) {
+    if (nbins[i] < 1 || nbins[i] > (1 << 24)) return arg_error("stream %d: nbins", i);
+    total += nbins[i];
+  }
+  for (int i = 0; i < m; ++i) {
+    P.kj[i].key_min = key_min[i];
+    P.kj[i].nbins = nbins[i];
+  }
+  for (int i = 0; i < 2 * m; ++i) {
+    P.sj[i / 2].key_min[i & 1] = key_min[m + i];
+    P.sj[i / 2].nbins[i & 1] = nbins[m + i];
+  }
+  return HIC_OK;
+}
+
+int hb_workspace(const void *workspace, size_t have, size_t need) {
+  if (!workspace) return arg_error("null pointer");
+  if (reinterpret_cast<uintptr_t>(workspace) % 16) return arg_error("workspace must be 16-byte aligned");
+  if (have < need) return arg_error("workspace too small");
+  return HIC_OK;
+}
+
+// the two tables into the workspace's head: one copy
+int hb_upload(const HbPlan &P, void *workspace, std::vector<char> &blob, const HsJob *&d_sj, const HkJob *&d_kj,
+              hipStream_t s) {
+  const size_t a = (size_t)round_up(P.sj.size() * sizeof(HsJob), 16);
+  blob.assign(hb_table_bytes(P.n), 0);
+  memcpy(blob.data(), P.sj.data(), P.sj.size() * sizeof(HsJob));
+  memcpy(blob.data() + a, P.kj.data(), P.kj.size() * sizeof(HkJob));
+  d_sj = static_cast<const HsJob *>(workspace);
+  d_kj = reinterpret_cast<const HkJob *>(static_cast<const char *>(workspace) + a);
+  return hip_status(hipMemcpyAsync(workspace, blob.data(), blob.size(), hipMemcpyHostToDevice, s), "hipMemcpyAsync");
+}
+
+// the histogram's per-workgroup bins behind the tables: `base` null = only the size (uint32 words)
+int64_t hb_hist_parts(HbPlan &P, uint32_t *base, int64_t &max_nbt, int &max_nwg, int64_t &max_part_bins) {
+  int64_t words = 0;
+  max_nbt = 0, max_nwg = 1, max_part_bins = 0;
+  const int g = P.sgrid();
+  for (auto &j : P.sj) {
+    const int64_t nbt = (int64_t)j.nbins[0] + j.nbins[1];
+    j.part = nullptr;
+    if (nbt > kHistLds) continue;  // the channel adds into its outputs with global atomics
+    j.part = base ? base + words : reinterpret_cast<uint32_t *>(16);
+    words += (int64_t)g * 2 * nbt;
+    max_nbt = nbt > max_nbt ? nbt : max_nbt;
+  }
+  for (auto &j : P.kj) {
+    const int64_t want = (j.n + kHT * 8 - 1) / (kHT * 8);
+    j.nwg = (int)(want < 2 * kHbGrid ? want : 2 * kHbGrid);
+    max_nwg = j.nwg > max_nwg ? j.nwg : max_nwg;
+    j.part = nullptr;
+    if (j.nbins > kHistLds || j.nwg == 1) continue;  // one workgroup's LDS bins go straight to the outputs
+    j.part = base ? base + words : reinterpret_cast<uint32_t *>(16);
+    words += (int64_t)j.nwg * 2 * j.nbins;
+    max_part_bins = j.nbins > max_part_bins ? j.nbins : max_part_bins;
+  }
+  return words;
+}
+
+int64_t hb_pack_words(const HbPlan &P) {
+  int64_t words = 8;
+  for (auto &j : P.sj) words += 2 * j.nrec;
+  for (auto &j : P.kj) words += (j.n + kHTile - 1) / kHTile;
+  return words;
+}
+
+}  // namespace
+
+extern "C" size_t hic_huffman_batch_key_range_workspace_bytes(int n) {
+  return n >= 1 && n <= HIC_SLOTS_BATCH_MAX ? hb_table_bytes(n) : 0;
+}
+
+extern "C" int hic_huffman_batch_key_range(int n, const hic_slot_job *jobs, const hic_key_stream *dc, int max_len,
+                                           int32_t *d_minmax, void *workspace, size_t workspace_bytes, void *stream) {
+  HbPlan P;
+  if (int e = hb_plan(n, jobs, dc, max_len, P)) return e;
+  if (!d_minmax) return arg_error("null pointer");
+  if (int e = hb_workspace(workspace, workspace_bytes, hb_table_bytes(n))) return e;
+  hipStream_t s = as_stream(stream);
+  std::vector<int32_t> init(18 * (size_t)n);
+  for (size_t i = 0; i < init.size(); ++i) init[i] = (i & 1) ? -2147483647 - 1 : 2147483647;
+  if (int e = hip_status(hipMemcpyAsync(d_minmax, init.data(), init.size() * 4, hipMemcpyHostToDevice, s),
+                         "hipMemcpyAsync"))
+    return e;
+  std::vector<char> blob;
+  const HsJob *d_sj;
+  const HkJob *d_kj;
+  if (int e = hb_upload(P, workspace, blob, d_sj, d_kj, s)) return e;
+  const int64_t want = (P.max_keys + 4 * kHT - 1) / (4 * kHT);
+  hipLaunchKernelGGL(k_key_range_table, dim3((unsigned)(want < kHbGrid ? want : kHbGrid), 3 * n), dim3(kHT), 0, s,
+                     d_kj, d_minmax);
+  if (int e = check_launch("k_key_range_table")) return e;
+  hipLaunchKernelGGL(k_slot_range<HsTable>, dim3(P.sgrid(), 3 * n), dim3(kHT), 0, s, HsTable{d_sj, max_len},
+                     d_minmax + 6 * n);
+  return check_launch("k_slot_range");
+}
+
+extern "C" size_t hic_huffman_batch_histogram_workspace_bytes(int n, const hic_slot_job *jobs,
+                                                              const hic_key_stream *dc, const int32_t *nbins) {
+  HbPlan P;
+  int64_t total, a, c;
+  int b;
+  if (hb_plan(n, jobs, dc, 15, P) || hb_bins(P, nbins, nbins, total)) return 0;
+  return hb_table_bytes(n) + (size_t)hb_hist_parts(P, nullptr, a, b, c) * 4;
+}
+
+extern "C" int hic_huffman_batch_histogram(int n, const hic_slot_job *jobs, const hic_key_stream *dc, int max_len,
+                                           const int32_t *key_min, const int32_t *nbins, uint32_t *d_counts,
+                                           uint32_t *d_first, void *workspace, size_t workspace_bytes, void *stream) {
+  HbPlan P;
+  int64_t total, max_nbt, max_part_bins;
+  int max_nwg;
+  if (int e = hb_plan(n, jobs, dc, max_len, P)) return e;
+  if (int e = hb_bins(P, key_min, nbins, total)) return e;
+  if (!d_counts || !d_first) return arg_error("null pointer");
+  if ((reinterpret_cast<uintptr_t>(d_counts) | reinterpret_cast<uintptr_t>(d_first)) % 4)
+    return arg_error("bins must be 4-byte aligned");
+  const size_t tb = hb_table_bytes(n);
+  const int64_t words = hb_hist_parts(P, nullptr, max_nbt, max_nwg, max_part_bins);
+  if (int e = hb_workspace(workspace, workspace_bytes, tb + (size_t)words * 4)) return e;
+  hb_hist_parts(P, reinterpret_cast<uint32_t *>(static_cast<char *>(workspace) + tb), max_nbt, max_nwg, max_part_bins);
+  int64_t off = 0;
+  for (int i = 0; i < 9 * n; ++i) {
+    if (i < 3 * n) {
+      P.kj[i].cnt = d_counts + off;
+      P.kj[i].first = d_first + off;
+    } else {
+      P.sj[(i - 3 * n) / 2].cnt[(i - 3 * n) & 1] = d_counts + off;
+      P.sj[(i - 3 * n) / 2].first[(i - 3 * n) & 1] = d_first + off;
+    }
+    off += nbins[i];
+  }
+  hipStream_t s = as_stream(stream);
+  if (int e = hip_status(hipMemsetAsync(d_counts, 0, (size_t)total * 4, s), "hipMemsetAsync")) return e;
+  if (int e = hip_status(hipMemsetAsync(d_first, 0xFF, (size_t)total * 4, s), "hipMemsetAsync")) return e;
+  std::vector<char> blob;
+  const HsJob *d_sj;
+  const HkJob *d_kj;
+  if (int e = hb_upload(P, workspace, blob, d_sj, d_kj, s)) return e;
+  hipLaunchKernelGGL(k_key_hist_table, dim3(max_nwg, 3 * n), dim3(kHT), 0, s, d_kj);
+  if (int e = check_launch("k_key_hist_table")) return e;
+  if (max_part_bins) {
+    hipLaunchKernelGGL(k_hist_reduce_table, dim3((unsigned)((max_part_bins + kHT - 1) / kHT), 3 * n), dim3(kHT), 0, s,
+                       d_kj);
+    if (int e = check_launch("k_hist_reduce_table")) return e;
+  }
+  const HsTable T{d_sj, max_len};
+  hipLaunchKernelGGL(k_slot_hist<HsTable>, dim3(P.sgrid(), 3 * n), dim3(kHT), 0, s, T);
+  if (int e = check_launch("k_slot_hist")) return e;
+  if (!max_nbt) return HIC_OK;
+  hipLaunchKernelGGL(k_slot_hist_reduce<HsTable>, dim3((unsigned)((max_nbt + kHT - 1) / kHT), 3 * n), dim3(kHT), 0, s,
+                     T, P.sgrid());
+  return check_launch("k_slot_hist_reduce");
+}
+
+extern "C" size_t hic_huffman_batch_pack_workspace_bytes(int n, const hic_slot_job *jobs, const hic_key_stream *dc) {
+  HbPlan P;
+  if (hb_plan(n, jobs, dc, 15, P)) return 0;
+  return hb_table_bytes(n) + (size_t)hb_pack_words(P) * sizeof(int64_t);
+}
+
+extern "C" int hic_huffman_batch_pack(int n, const hic_slot_job *jobs, const hic_key_stream *dc, int max_len,
+                                      const int32_t *key_min, const int32_t *nbins, const uint64_t *d_code_bits,
+                                      const uint8_t *d_code_len, uint8_t *d_out, const int64_t *out_bytes,
+                                      int64_t *d_nbits, void *workspace, size_t workspace_bytes, void *stream) {
+  HbPlan P;
+  int64_t total;
+  if (int e = hb_plan(n, jobs, dc, max_len, P)) return e;
+  if (int e = hb_bins(P, key_min, nbins, total)) return e;
+  if (!d_code_bits || !d_code_len || !d_out || !out_bytes || !d_nbits) return arg_error("null pointer");
+  if (reinterpret_cast<uintptr_t>(d_code_bits) % 8 || reinterpret_cast<uintptr_t>(d_nbits) % 8)
+    return arg_error("code bits and bit counts must be 8-byte aligned");
+  if (reinterpret_cast<uintptr_t>(d_out) % 4) return arg_error("out must be 4-byte aligned and sized");
+  const size_t tb = hb_table_bytes(n);
+  if (int e = hb_workspace(workspace, workspace_bytes, tb + (size_t)hb_pack_words(P) * sizeof(int64_t))) return e;
+  int64_t *ws = reinterpret_cast<int64_t *>(static_cast<char *>(workspace) + tb);
+  int64_t bin = 0, byte = 0, max_nt = 1;
+  for (int i = 0; i < 9 * n; ++i) {
+    if (out_bytes[i] % 4 || out_bytes[i] <= 0) return arg_error("stream %d: out must be 4-byte aligned and sized", i);
+    uint32_t *out = reinterpret_cast<uint32_t *>(d_out + byte);
+    if (i < 3 * n) {
+      HkJob &j = P.kj[i];
+      j.cbits = d_code_bits + bin;
+      j.clen = d_code_len + bin;
+      j.out = out;
+      j.out_words = out_bytes[i] / 4;
+      j.nt = (int)((j.n + kHTile - 1) / kHTile);
+      j.tile = ws;
+      ws += j.nt;
+      j.d_nbits = d_nbits + i;
+      max_nt = j.nt > max_nt ? j.nt : max_nt;
+    } else {
+      const int c = (i - 3 * n) / 2, w = (i - 3 * n) & 1;
+      HsJob &j = P.sj[c];
+      j.cbits[w] = d_code_bits + bin;
+      j.clen[w] = d_code_len + bin;
+      j.out[w] = out;
+      j.out_words[w] = out_bytes[i] / 4;
+      j.bits[w] = ws;
+      ws += j.nrec;
+      j.d_nbits = d_nbits + 3 * n + 2 * c;
+    }
+    bin += nbins[i];
+    byte += out_bytes[i];
+  }
+  hipStream_t s = as_stream(stream);
+  if (int e = hip_status(hipMemsetAsync(d_out, 0, (size_t)byte, s), "hipMemsetAsync")) return e;
+  std::vector<char> blob;
+  const HsJob *d_sj;
+  const HkJob *d_kj;
+  if (int e = hb_upload(P, workspace, blob, d_sj, d_kj, s)) return e;
+  hipLaunchKernelGGL(k_pack_sizes_table, dim3((unsigned)max_nt, 3 * n), dim3(kHT), 0, s, d_kj);
+  hipLaunchKernelGGL(k_pack_scan_table, dim3(1, 3 * n), dim3(kHT), 0, s, d_kj);
+  hipLaunchKernelGGL(k_pack_bits_table, dim3((unsigned)max_nt, 3 * n), dim3(kHT), kPackWords * sizeof(uint32_t), s,
+                     d_kj);
+  if (int e = check_launch("k_pack_bits_table")) return e;
+  const HsTable T{d_sj, max_len};
+  hipLaunchKernelGGL(k_slot_pack_sizes<HsTable>, dim3((unsigned)P.max_nrec, 3 * n), dim3(kHT), 0, s, T);
+  hipLaunchKernelGGL(k_slot_pack_scan<HsTable>, dim3(2, 3 * n), dim3(kHT), 0, s, T);
+  hipLaunchKernelGGL(k_slot_pack_bits<HsTable>, dim3((unsigned)P.max_nrec, 3 * n), dim3(kHT),
+                     kPackWords * sizeof(uint32_t), s, T);
+  const int64_t batches = (P.max_nrec + kHT - 1) / kHT;
+  hipLaunchKernelGGL(k_slot_pack_fill<HsTable>, dim3((unsigned)(batches * 8 < kHbGrid ? batches * 8 : kHbGrid), 3 * n),
+                     dim3(kHT), 0, s, T);
   return check_launch("k_slot_pack_fill");
 }

@@ -15,6 +15,11 @@
 // reads "1" (translate_path, huffman.py:119-129); one leaf alone is the left child
 // of a singleton root: code "1".
 //
+// hic_huffman_build_batch builds the trees of m streams from their histogram bins
+// in one call: per stream the present bins in first-appearance order (np.flatnonzero
+// + a stable argsort by `first`, what huffman.DeviceStreams does per stream in numpy)
+// and hic_huffman_build's codes of them.
+//
 // hic_huffman_from_codes restates construct_from_coding (huffman.py:30-58) for a
 // complete prefix code -- what every encoder table is -- and lays the tree out as
 // hic_huffman_decode takes it (breadth first, huffman.HuffmanTree.flat).  Any other
@@ -24,6 +29,7 @@
 // behave as the reference's do.
 #include <string.h>
 
+#include <algorithm>
 #include <vector>
 
 #include "hic_common.h"
@@ -88,14 +94,11 @@ static void code_text(const uint8_t *len, const uint64_t *code, int64_t n, char 
   }
 }
 
-extern "C" int hic_huffman_build(const int64_t *h_counts, int64_t n, uint8_t *h_len, uint64_t *h_code,
-                                 char *h_text) {
-  if (!h_counts || !h_len || !h_code) return hic::arg_error("null pointer");
-  if (n < 1 || n > (int64_t)1 << 30) return hic::arg_error("leaf count %lld", (long long)n);
+// the codes of n >= 1 leaves (hic_huffman_build's, without its text)
+static int build_codes(const int64_t *h_counts, int64_t n, uint8_t *h_len, uint64_t *h_code) {
   if (n == 1) {  // Node.singleton: the leaf is the root's left child
     h_len[0] = 1;
     h_code[0] = 1;
-    if (h_text) code_text(h_len, h_code, 1, h_text);
     return HIC_OK;
   }
   const int64_t nodes = 2 * n - 1;
@@ -135,7 +138,62 @@ extern "C" int hic_huffman_build(const int64_t *h_counts, int64_t n, uint8_t *h_
     st.push_back({kid[2 * k], it.len + 1, it.bits << 1 | 1});
     st.push_back({kid[2 * k + 1], it.len + 1, it.bits << 1});
   }
+  return HIC_OK;
+}
+
+extern "C" int hic_huffman_build(const int64_t *h_counts, int64_t n, uint8_t *h_len, uint64_t *h_code,
+                                 char *h_text) {
+  if (!h_counts || !h_len || !h_code) return hic::arg_error("null pointer");
+  if (n < 1 || n > (int64_t)1 << 30) return hic::arg_error("leaf count %lld", (long long)n);
+  if (int e = build_codes(h_counts, n, h_len, h_code)) return e;
   if (h_text) code_text(h_len, h_code, n, h_text);
+  return HIC_OK;
+}
+
+extern "C" int hic_huffman_build_batch(int64_t m, const uint32_t *h_counts, const uint32_t *h_first,
+                                       const int64_t *h_bin_off, int64_t *h_leaf_off, int32_t *h_bins,
+                                       uint8_t *h_len, uint64_t *h_code, char *h_text, int64_t text_cap,
+                                       int64_t *h_text_off) {
+  if (!h_counts || !h_first || !h_bin_off || !h_leaf_off || !h_bins || !h_len || !h_code)
+    return hic::arg_error("null pointer");
+  if (h_text && !h_text_off) return hic::arg_error("null pointer");
+  if (m < 1 || m > (int64_t)1 << 30) return hic::arg_error("stream count %lld", (long long)m);
+  if (h_bin_off[0] != 0) return hic::arg_error("bin offsets start at 0");
+  for (int64_t i = 0; i < m; ++i)
+    if (h_bin_off[i + 1] <= h_bin_off[i] || h_bin_off[i + 1] - h_bin_off[i] > (1 << 24))
+      return hic::arg_error("stream %lld: nbins", (long long)i);
+  std::vector<int32_t> order;
+  std::vector<int64_t> cnt;
+  int64_t leaf = 0, text = 0;
+  for (int64_t i = 0; i < m; ++i) {
+    const uint32_t *c = h_counts + h_bin_off[i], *f = h_first + h_bin_off[i];
+    const int32_t nb = (int32_t)(h_bin_off[i + 1] - h_bin_off[i]);
+    // np.flatnonzero, then a stable argsort by first
+    order.clear();
+    for (int32_t b = 0; b < nb; ++b)
+      if (c[b]) order.push_back(b);
+    if (order.empty()) return hic::arg_error("stream %lld: no key present", (long long)i);
+    std::stable_sort(order.begin(), order.end(), [f](int32_t a, int32_t b) { return f[a] < f[b]; });
+    const int64_t n = (int64_t)order.size();
+    cnt.resize(n);
+    for (int64_t k = 0; k < n; ++k) {
+      cnt[k] = c[order[k]];
+      h_bins[leaf + k] = order[k];
+    }
+    h_leaf_off[i] = leaf;
+    if (int e = build_codes(cnt.data(), n, h_len + leaf, h_code + leaf)) return e;
+    if (h_text) {
+      int64_t need = n;
+      for (int64_t k = 0; k < n; ++k) need += h_len[leaf + k];
+      if (text + need > text_cap) return hic::arg_error("text buffer too small");
+      code_text(h_len + leaf, h_code + leaf, n, h_text + text);
+      h_text_off[i] = text;
+      text += need;
+    }
+    leaf += n;
+  }
+  h_leaf_off[m] = leaf;
+  if (h_text) h_text_off[m] = text;
   return HIC_OK;
 }
 

@@ -743,3 +743,151 @@ class DeviceStreams:
                 res.append((h[boff[i]:boff[i] + -(-int(nb[i]) // 8)], int(nb[i])))
             return res
         return collect
+
+
+class _BatchCodes(CodeBook):
+    """A CodeBook whose codes hic_huffman_build_batch built (BatchStreams)."""
+
+    def __init__(self, keys, lens, bits, strs):
+        self.leaf_keys, self.lens, self.bits, self._strs = keys, lens, bits, strs
+
+
+class BatchStreams:
+    """The Huffman stage of n slot-layout images of one batch (pipeline.BatchEncoder):
+    the same trees and packed bits as one DeviceStreams per image, with a number of
+    library calls, launches and host reads that does not grow with n.  Each phase is
+    one call over all 9 n streams (hic_huffman_batch_key_range / _histogram / _pack,
+    csrc/huffman.hip: the jobs in a table in device memory); the 9 n trees come from
+    one native call (hic_huffman_build_batch); the host reads three times: every key
+    range, every histogram, every stream's bits with the bit counts behind them.
+
+    dcs[i]: image i's three DC tensors (int32, Y Cr Cb); jobs[i]: its three
+    _lib.SlotJob after the close; counts[i]: its three symbol counts.  Per image the
+    nine streams are in payload order (DC, AC values, AC lengths; Y Cr Cb inside):
+    lo[i][p], nbins[i][p], counts[i][p], trees[i][p] (encode_table, code_table), and
+    packed()[i][p] = (packed uint8 array, bits)."""
+
+    def __init__(self, dcs, jobs, counts, stream=None):
+        n = self.n = len(dcs)
+        if n < 1 or len(jobs) != n or len(counts) != n:
+            raise ValueError("one entry per image")
+        if min(int(c) for cs in counts for c in cs) == 0 or min(t.numel() for ts in dcs for t in ts) == 0:
+            raise ValueError("empty key stream")
+        if any(t.dtype != torch.int32 for ts in dcs for t in ts):
+            raise ValueError("DC streams are int32")
+        self.stream = stream
+        self._dcs = dcs  # (kept alive: the tables below hold their addresses)
+        self._jobs = (_lib.SlotJob * (3 * n))(*[j for js in jobs for j in js])
+        self._dc = (_lib.KeyStream * (3 * n))(*[_lib.KeyStream(t.data_ptr(), t.numel()) for ts in dcs for t in ts])
+        # payload position p of image i -> the batch's stream (include/hiccup_hip.h)
+        self._row = np.array([[3 * i + p if p < 3 else 3 * n + 2 * (3 * i + p % 3) + (1 if p < 6 else 0)
+                               for p in range(9)] for i in range(n)], dtype=np.int64)
+        with device.on_stream(stream):
+            self._histograms()
+
+    def _per_image(self, per_stream):
+        return [[per_stream[r] for r in rows] for rows in self._row.tolist()]
+
+    def _histograms(self):
+        lib, n, s = _lib.load(), self.n, device.stream_ptr(self.stream)
+        m = 9 * n
+        i32p = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+        mm = device.empty((m, 2), torch.int32)
+        nb = lib.hic_huffman_batch_key_range_workspace_bytes(n)
+        ws = device.empty((nb,), torch.uint8)
+        _lib.call("hic_huffman_batch_key_range", n, self._jobs, self._dc, 15, device.ptr(mm), device.ptr(ws), nb, s)
+        rng = mm.cpu().numpy()  # host read 1: every key range
+        self._lo = np.ascontiguousarray(rng[:, 0], dtype=np.int32)
+        self._nbins = np.ascontiguousarray(rng[:, 1] - rng[:, 0] + 1, dtype=np.int32)
+        off = self._off = np.concatenate([[0], np.cumsum(self._nbins, dtype=np.int64)]).astype(np.int64)
+        total = int(off[-1])
+        bins = device.empty((2, total), torch.int32)
+        nb = lib.hic_huffman_batch_histogram_workspace_bytes(n, self._jobs, self._dc, i32p(self._nbins))
+        ws = device.empty((max(nb, 16),), torch.uint8)
+        _lib.call("hic_huffman_batch_histogram", n, self._jobs, self._dc, 15, i32p(self._lo), i32p(self._nbins),
+                  device.ptr(bins[0]), device.ptr(bins[1]), device.ptr(ws), nb, s)
+        h = bins.cpu().numpy().view(np.uint32)  # host read 2: every histogram
+        c_all, f_all = np.ascontiguousarray(h[0]), np.ascontiguousarray(h[1])
+        # all 9 n trees in one native call
+        leaf_off = np.empty(m + 1, np.int64)
+        text_off = np.empty(m + 1, np.int64)
+        order = np.empty(total, np.int32)
+        lens = np.empty(total, np.uint8)
+        bits = np.empty(total, np.uint64)
+        text = np.empty(65 * total, np.uint8)
+        _lib.call("hic_huffman_build_batch", m, i32p(c_all), i32p(f_all), i32p(off), i32p(leaf_off), i32p(order),
+                  i32p(lens), i32p(bits), i32p(text), text.size, i32p(text_off))
+        nleaf = int(leaf_off[-1])
+        order, lens, bits = order[:nleaf], lens[:nleaf], bits[:nleaf]
+        gidx = order.astype(np.int64) + np.repeat(off[:-1], np.diff(leaf_off))  # each leaf's bin in the batch's layout
+        keys = (order.astype(np.int64) + np.repeat(self._lo.astype(np.int64), np.diff(leaf_off))).tolist()
+        # the code tables in the bin layout (0 / 0: a key not in the tree) and each stream's bits
+        self._cb = np.zeros(total, np.uint64)
+        self._cl = np.zeros(total, np.uint8)
+        self._cb[gidx] = bits
+        self._cl[gidx] = lens
+        self._totals = np.add.reduceat(c_all[gidx].astype(np.int64) * lens.astype(np.int64), leaf_off[:-1])
+        strs = text[:int(text_off[-1])].tobytes().decode("ascii").split()
+        lo_l = leaf_off.tolist()
+        trees = [_BatchCodes(keys[a:b], lens[a:b], bits[a:b], strs[a:b]) for a, b in zip(lo_l[:-1], lo_l[1:])]
+        ol = off.tolist()
+        self.trees = self._per_image(trees)
+        self.counts = self._per_image([c_all[a:b] for a, b in zip(ol[:-1], ol[1:])])
+        self.first = self._per_image([f_all[a:b] for a, b in zip(ol[:-1], ol[1:])])
+        self.lo = self._per_image(self._lo.tolist())
+        self.nbins = self._per_image(self._nbins.tolist())
+
+    def packed(self):
+        """Per image its nine (packed uint8 numpy array, number of bits)."""
+        return self.packed_start()()
+
+    def packed_start(self):
+        """packed() in two halves, as DeviceStreams.packed_start: the packing and its
+        one copy back are queued now, the returned function waits for them."""
+        with device.on_stream(self.stream):
+            return self._packed()
+
+    def _packed(self):
+        lib, n, s = _lib.load(), self.n, device.stream_ptr(self.stream)
+        m = 9 * n
+        vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+        totals = self._totals
+        nbytes = np.maximum(4, -(-totals // 32) * 4).astype(np.int64)
+        boff = np.concatenate([[0], np.cumsum(nbytes)]).astype(np.int64)
+        T, nout = int(self._off[-1]), -(-int(boff[-1]) // 8) * 8
+        # one upload: the code bits, then the code lengths
+        tabs = device.to_device(np.concatenate([self._cb.view(np.uint8), self._cl]))
+        # one buffer: every stream's bits, then (8-byte aligned) the 9 n bit counts
+        out = device.empty((nout + 8 * m,), torch.uint8)
+        nb = lib.hic_huffman_batch_pack_workspace_bytes(n, self._jobs, self._dc)
+        ws = device.empty((nb,), torch.uint8)
+        _lib.call("hic_huffman_batch_pack", n, self._jobs, self._dc, 15, vp(self._lo), vp(self._nbins),
+                  ctypes.c_void_p(tabs.data_ptr()), ctypes.c_void_p(tabs.data_ptr() + 8 * T), device.ptr(out),
+                  vp(nbytes), ctypes.c_void_p(out.data_ptr() + nout), device.ptr(ws), nb, s)
+        cur = self.stream if self.stream is not None else torch.cuda.current_stream()
+        host = device.host_empty((out.numel(),), np.uint8)
+        pinned = device._is_pinned(host)
+        with torch.cuda.stream(cur):
+            if pinned:
+                torch.from_numpy(host).copy_(out, non_blocking=True)
+            done = torch.cuda.Event()
+            done.record(cur)
+        rows = self._row.tolist()
+
+        def collect(_keep=(tabs, ws)):  # (alive until the packing has run)
+            done.synchronize()
+            h = host if pinned else out.cpu().numpy()  # host read 3: the bits and the bit counts
+            nbits = h[nout:].view(np.int64).tolist()
+            bo = boff.tolist()
+            tl = totals.tolist()
+            res = []
+            for i in range(n):
+                one = []
+                for r in rows[i]:
+                    if nbits[r] != tl[r]:
+                        raise RuntimeError("image %d stream %d: packed %d bits, the histogram says %d"
+                                           % (i, r, nbits[r], tl[r]))
+                    one.append((h[bo[r]:bo[r] + -(-nbits[r] // 8)], nbits[r]))
+                res.append(one)
+            return res
+        return collect

@@ -489,6 +489,14 @@ def batch_slots_eligible(n, H, W, max_len=15):
     return n * bands * 4 <= (2**31 - 1) // 64 and n * parts <= (2**31 - 1) // 64
 
 
+def batched_default(n, H, W):
+    """What BatchEncoder.hic_images(batched=None) resolves to for n images of H x W:
+    the batched Huffman stage wherever its measured range lay at or below the
+    per-image loop's on the parent commit -- every measured batch, 64 x 512^2 down to
+    one 8K image (profiles/r17/huffman_batch/)."""
+    return True
+
+
 class BatchEncoder:
     """n images of one shape in the slot layout, encoded by ONE fused launch
     (hic_encode420_slots_batch_u8) and closed by ONE scan launch
@@ -558,9 +566,17 @@ class BatchEncoder:
         self.transform(rgb, stream, dct_events=dct_events)
         self.entropy(stream)
 
-    def hic_images(self, stream=None, from_slots=True):
-        """[batch[i].hic_image(stream, from_slots)]: one read of the batch's counts, then
-        the per-image Huffman stage (nine trees per image on the host; syncs)."""
+    def hic_images(self, stream=None, from_slots=True, batched=None):
+        """[batch[i].hic_image(stream, from_slots)] (syncs): one read of the batch's
+        counts, then the Huffman stage.  batched=True: one pass per phase over all 9 n
+        streams (huffman.BatchStreams: a number of library calls and host reads that
+        does not grow with n; needs from_slots); False: the per-image stage, one
+        huffman.DeviceStreams each; None: the measured default (batched_default).
+        Byte for byte the same images either way."""
+        if batched is None:
+            batched = bool(from_slots) and batched_default(self.n, self.H, self.W)
+        if batched and not from_slots:
+            raise ValueError("the batched Huffman stage reads the slot layout: batched=True needs from_slots=True")
         if not from_slots:
             for e in self.encoders:
                 e.compact(stream)
@@ -569,7 +585,34 @@ class BatchEncoder:
             for c in counts:
                 for v, k in zip(c, CHANNELS):
                     check_count(int(v), k)
+            if batched:
+                return self._hic_images_batched(stream, counts)
             return [e._hic_image(stream, bool(from_slots), counts[i]) for i, e in enumerate(self.encoders)]
+
+    def _hic_images_batched(self, stream, counts):
+        from . import huffman
+        bs = huffman.BatchStreams([[e.dc[k] for k in CHANNELS] for e in self.encoders],
+                                  [e._slot_jobs() for e in self.encoders], counts, stream=stream)
+        collect = bs.packed_start()
+        tables = self._tables(bs.trees)  # (while the GPU packs)
+        return self._assemble(bs.trees, collect(), tables)
+
+    @staticmethod
+    def _tables(trees):
+        """The table payloads, per image as Encoder._hic_image builds them (DC keys
+        numpy int32, AC keys int: part of the byte format)."""
+        from . import hicimage as hic
+        return [[hic.PayloadStringP(hic.TupP, [hic.TupP(np.int32(v) if p < 3 else int(v), c)
+                                               for v, c in t[p].encode_table()]) for p in range(9)] for t in trees]
+
+    def _assemble(self, trees, packed, tables=None):
+        """The batch's HicImages from its trees and packed streams: all that the
+        batched stage leaves to Python."""
+        from . import hicimage as hic
+        tables = self._tables(trees) if tables is None else tables
+        (h, w), (hc, wc) = self.encoders[0].shapes["lum"], self.encoders[0].shapes["cr"]
+        return [hic.HicImage.jpeg_image(tables[i] + [hic.BitStringP.from_packed(*pk) for pk in one]
+                                        + [hic.TupP(h, w), hic.TupP(hc, wc)]) for i, one in enumerate(packed)]
 
 
 class Decoder:

@@ -299,6 +299,47 @@ int hic_slot_huffman_pack(int n, const hic_slot_job *jobs, int max_len, const in
                           const int32_t *nbins, const uint64_t *const *h_code_bits,
                           const uint8_t *const *h_code_len, uint8_t *const *h_out, const int64_t *out_bytes,
                           int64_t *d_nbits, void *workspace, void *stream);
+/* ---- batched Huffman encode (round 17): the 9 n key streams of n images closed by
+ *      hic_rle_slots_close[_batch], one pass per phase -- a fixed number of launches,
+ *      memsets and copies whatever n is.  Per stream the results are exactly those of
+ *      hic_key_range / hic_key_histogram / hic_huffman_pack (DC streams) and of
+ *      hic_slot_key_range / hic_slot_key_histogram / hic_slot_huffman_pack (slot
+ *      streams) called per image; positions, bins and bits are per stream.
+ *  jobs[3 i + k] = image i's Y, Cr, Cb slot job, dc[3 i + k] = that channel's DC
+ *  stream (int32 keys, 16-byte aligned, 1 <= n <= INT32_MAX).  Stream order of every
+ *  per-stream array (9 n entries): the 3 n DC streams, then per channel c = 3 i + k
+ *  its lengths (3 n + 2 c) and its values (3 n + 2 c + 1).  Bins (d_counts, d_first,
+ *  d_code_bits, d_code_len) lie back to back in stream order, stream s's at the sum
+ *  of the nbins before it; so do the outputs (d_out, at the sum of the out_bytes
+ *  before).  The library allocates nothing: the per-phase job tables and all scratch
+ *  live in the caller's workspace (16-byte aligned, >= the phase's
+ *  *_workspace_bytes, which are 0 for arguments the call would refuse).
+ *  Everything is checked before any device call (HIC_ERR_ARG, nothing launched): n
+ *  outside 1 .. HIC_SLOTS_BATCH_MAX, max_len other than 15, every slot job as
+ *  hic_slot_key_range checks it, null or misaligned pointers, nbins outside 1 .. 2^24,
+ *  out_bytes not a positive multiple of 4, a workspace that is too small.
+ *  hic_huffman_batch_key_range: d_minmax (device int32[18 n]) = {min, max} per stream.
+ *  hic_huffman_batch_histogram: d_counts / d_first (uint32, sum of nbins entries each)
+ *    as hic_key_histogram / hic_slot_key_histogram define them.
+ *  hic_huffman_batch_pack: d_out (4-byte aligned, zeroed here) and d_nbits (device
+ *    int64[9 n]) as hic_huffman_pack / hic_slot_huffman_pack define them. */
+typedef struct {
+  const int32_t *keys; /* n int32 keys, 16-byte aligned */
+  int64_t n;
+} hic_key_stream;
+size_t hic_huffman_batch_key_range_workspace_bytes(int n);
+int hic_huffman_batch_key_range(int n, const hic_slot_job *jobs, const hic_key_stream *dc, int max_len,
+                                int32_t *d_minmax, void *workspace, size_t workspace_bytes, void *stream);
+size_t hic_huffman_batch_histogram_workspace_bytes(int n, const hic_slot_job *jobs, const hic_key_stream *dc,
+                                                   const int32_t *nbins);
+int hic_huffman_batch_histogram(int n, const hic_slot_job *jobs, const hic_key_stream *dc, int max_len,
+                                const int32_t *key_min, const int32_t *nbins, uint32_t *d_counts, uint32_t *d_first,
+                                void *workspace, size_t workspace_bytes, void *stream);
+size_t hic_huffman_batch_pack_workspace_bytes(int n, const hic_slot_job *jobs, const hic_key_stream *dc);
+int hic_huffman_batch_pack(int n, const hic_slot_job *jobs, const hic_key_stream *dc, int max_len,
+                           const int32_t *key_min, const int32_t *nbins, const uint64_t *d_code_bits,
+                           const uint8_t *d_code_len, uint8_t *d_out, const int64_t *out_bytes, int64_t *d_nbits,
+                           void *workspace, size_t workspace_bytes, void *stream);
 int hic_rle_decode_i16_slots(const uint8_t *slot_len, const int16_t *slot_val, const int64_t *d_nsym,
                              const int32_t *dc_diff, int64_t nblk, int records_per_tile, const int32_t *d_index,
                              int16_t *blocks, int64_t *d_status, void *stream);
@@ -732,6 +773,17 @@ int hic_huffman_decode_batch(int n, hic_huffman_decode_job *jobs, void *stream);
  *    the edge at the root).  One leaf: code "1".  HIC_ERR_ARG if a code would pass
  *    64 bits (needs > 2^44 symbols).  h_text (may be null; >= 65 n bytes): the
  *    codes as text, each followed by one space.
+ *  hic_huffman_build_batch: the trees of m streams from their histogram bins (as
+ *    hic_key_histogram writes them: count and first-appearance index per bin), stream
+ *    i's bins at h_counts / h_first + h_bin_off[i] .. h_bin_off[i + 1] (h_bin_off[0] =
+ *    0, 1 .. 2^24 bins each, at least one present).  Per stream: its present bins in
+ *    first-appearance order (ties by bin: numpy's flatnonzero + stable argsort) into
+ *    h_bins + h_leaf_off[i] (h_leaf_off: m + 1 entries, out), and hic_huffman_build's
+ *    codes of them, leaf for leaf, into h_len / h_code at the same index (each array:
+ *    room for one entry per bin).  h_text (may be null): every stream's codes as
+ *    text, each followed by one space, stream i's at h_text_off[i] .. h_text_off[i + 1]
+ *    (m + 1 entries); HIC_ERR_ARG when text_cap bytes do not hold them (65 per present
+ *    key always do).
  *  hic_huffman_from_codes: construct_from_coding (huffman.py:30-58) + the
  *    breadth-first layout hic_huffman_decode takes, for a table of n >= 2 codes
  *    that is a complete prefix code: code i is h_chars[h_off[i] .. h_off[i + 1])
@@ -741,6 +793,9 @@ int hic_huffman_decode_batch(int n, hic_huffman_decode_job *jobs, void *stream);
  *    order, *h_minlen the shortest code.  Any other table: HIC_ERR_ARG ("irregular
  *    table ..."), nothing written; the caller then builds the reference's own tree. */
 int hic_huffman_build(const int64_t *h_counts, int64_t n, uint8_t *h_len, uint64_t *h_code, char *h_text);
+int hic_huffman_build_batch(int64_t m, const uint32_t *h_counts, const uint32_t *h_first, const int64_t *h_bin_off,
+                            int64_t *h_leaf_off, int32_t *h_bins, uint8_t *h_len, uint64_t *h_code, char *h_text,
+                            int64_t text_cap, int64_t *h_text_off);
 int hic_huffman_from_codes(const char *h_chars, const int64_t *h_off, int64_t n, int32_t *h_child,
                            int32_t *h_leaf_seg, int64_t *h_nodes, int32_t *h_minlen);
 
