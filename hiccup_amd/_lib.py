@@ -101,6 +101,28 @@ class DecodeImage(ctypes.Structure):
     _fields_ = [("c", DecodePlane * 3)]
 
 
+class WinGeo(ctypes.Structure):
+    """WinGeo (csrc/decode_batch.h): the kernels' geometry of one window launch."""
+    _fields_ = [(f, _int) for f in ("bi0", "nrows", "bj0", "bj1", "tpr", "oy", "ox", "cy0", "cx0", "ch", "cw",
+                                    "cpitch")] + [("n_ac", _i64)]
+
+
+class DecodeWindowEntry(ctypes.Structure):
+    """DecWinBatchEntry (csrc/decode_batch.h): one image of a batched region decode's table."""
+    _fields_ = [("c", DecodePlane * 3), ("g", WinGeo * 2), ("y0", ctypes.c_int32), ("x0", ctypes.c_int32),
+                ("pad", _i64 * 28)]
+
+
+class DecodeWindowHeader(ctypes.Structure):
+    """DecWinBatchHeader (csrc/decode_batch.h)."""
+    _fields_ = [("magic", ctypes.c_uint64), ("kind", ctypes.c_int32), ("n", ctypes.c_int32), ("H", _i64), ("W", _i64),
+                ("h", _i64), ("w", _i64), ("out_row_stride", _i64), ("chroma_pitch", _i64), ("chroma_rows", _i64),
+                ("waves_y", ctypes.c_int32), ("waves_c", ctypes.c_int32), ("grid_y", ctypes.c_int32),
+                ("grid_c", ctypes.c_int32), ("nblk_y", _i64), ("nblk_c", _i64), ("pad", _i64 * 3)]
+
+
+assert ctypes.sizeof(DecodeWindowEntry) == 512 and ctypes.sizeof(DecodeWindowHeader) == 128
+
 SIGNATURES = {
     "hic_abi_version": (_int, []),
     "hic_last_error": (_int, [ctypes.c_char_p, _sz]),
@@ -187,6 +209,9 @@ SIGNATURES = {
     "hic_decode_batch_table_bytes": (_sz, [_int]),
     "hic_decode_batch_table": (_int, [_int, _int, _i64, _i64, _i64, _i64, _vp, _vp, _sz]),
     "hic_decode420_batch_u8": (_int, [_vp, _vp, _vp]),
+    "hic_decode_window_batch_table_bytes": (_sz, [_int]),
+    "hic_decode_window_batch_table": (_int, [_int, _int, _i64, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _vp, _sz]),
+    "hic_decode420_window_batch_u8": (_int, [_vp, _vp, _vp]),
     "hic_event_create": (_int, [_vp]),
     "hic_event_destroy": (_int, [_vp]),
     "hic_event_elapsed_ms": (_int, [_vp, _vp, _vp]),

@@ -757,6 +757,57 @@ def decode_region(hic_image, y0, x0, h, w):
     return open(hic_image).decode_region(y0, x0, h, w)
 
 
+def decode_regions_device(images, origins, h, w):
+    """decode_regions with the result left on the device: one (n, h, w, 3) uint8 tensor."""
+    from . import pipeline
+    images, origins = list(images), [(int(y0), int(x0)) for y0, x0 in origins]
+    if len(images) != len(origins):
+        raise ValueError("%d origins for %d images" % (len(origins), len(images)))
+    for f, (y0, x0) in zip(images, origins):
+        # a file whose header the fast path takes states its shape: checked before it is opened
+        head = None if isinstance(f, OpenImage) else _fast_header(f)
+        H, W = f.shape[:2] if isinstance(f, OpenImage) else (head[:2] if head is not None else (None, None))
+        if H is not None and (min(h, w) < 1 or y0 < 0 or x0 < 0 or y0 + h > H or x0 + w > W):
+            raise ValueError("window (%d, %d, %d, %d) outside the %d x %d image" % (y0, x0, h, w, H, W))
+    with _gc_paused():
+        opened = [f if isinstance(f, OpenImage) else OpenImage(f) for f in images]
+    for o, (y0, x0) in zip(opened, origins):  # every window, before any GPU work of the decode
+        o._check(y0, x0, h, w)
+    out = device.empty((len(opened), h, w, 3), torch.uint8)
+    groups = {}
+    for i, o in enumerate(opened):
+        if o._streams is not None:
+            groups.setdefault(o.shape[:2], []).append(i)
+    done = set()
+    for (H, W), members in groups.items():
+        for at in range(0, len(members), pipeline.DECODE_BATCH_MAX):
+            part = members[at:at + pipeline.DECODE_BATCH_MAX]
+            if not pipeline.batch_region_eligible(len(part), H, W, h, w):
+                continue
+            whole = len(part) == len(opened)  # one group: straight into the result
+            dec = pipeline.BatchRegionDecoder(len(part), H, W, h, w, out=out if whole else None)
+            got = dec.decode([opened[i]._streams for i in part], [origins[i] for i in part])
+            if not whole:
+                out[torch.as_tensor(part, device=out.device)] = got
+            done.update(part)
+    for i, o in enumerate(opened):  # the whole-decode fallback's files, and a group the batch refuses
+        if i not in done:
+            out[i] = o.decode_region_device(*origins[i], h, w)
+    return out
+
+
+def decode_regions(images, origins, h, w):
+    """np.stack([decode_region(f, y0, x0, h, w) for f, (y0, x0) in zip(images, origins)]):
+    an h x w window from each image, image i's at origins[i].  images: HicImages, or
+    OpenImages (codec.open: the symbols and tile index already on the device).  The
+    images are grouped by shape and each group whose members have device streams is
+    decoded by ONE pipeline.BatchRegionDecoder call (two launches, the crops stored
+    straight into the result); a file that took OpenImage's whole-decode fallback, and a
+    group the batch refuses, are served per image.  A window outside its image raises
+    ValueError before any GPU work of the decode."""
+    return device.to_host(decode_regions_device(images, origins, h, w))
+
+
 # ------------------------------------------------------------------ out of scope
 def wavelet_encode(compressed):
     raise NotImplementedError(_OUT_OF_SCOPE)

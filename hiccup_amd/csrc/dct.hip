@@ -325,24 +325,31 @@ constexpr int kRowI16 = 68;  // LDS block row: 64 slots + pad (136 B, conflict-f
 // (a no-op for a block inside the window and for its left / right neighbour, whose
 // columns the span holds by construction) and their stores are gated: a lane stores
 // only a block of the wave's own block row wbi inside columns [g.bj0, g.bj1).
-struct NoWin {};
-struct WinGeo {
-  int bi0, nrows, bj0, bj1;  // the launch plane's block rows [bi0, bi0 + nrows), columns [bj0, bj1)
-  int tpr;                   // waves per block row (the most tiles a row's columns touch)
-  int oy, ox;                // the plane coordinates of out's first sample
-  int cy0, cx0, ch, cw;      // RGB form: the chroma planes' span
-  int cpitch;
-  int64_t n_ac;              // *d_status of a good launch: 63 per block of the window
-};
+//
+// The cropped form (CROP, with WIN; the batched region decode): rgb is a crop_h x
+// crop_w x 3 result whose first pixel is image pixel (g.oy, g.ox), any pixel of the
+// image, so a block of the aligned window may lie partly or wholly outside it and the
+// address of a lane's 24 row bytes has any alignment.  A lane stores only its own bytes
+// that fall inside the result: rows [0, crop_h), row bytes [0, 3 crop_w).  Its dwords
+// that lie whole inside go out as dword stores at their own byte address (no alignment
+// is promised to the compiler, which emits the store the target allows there; global
+// memory takes misaligned dwords); a dword cut by the result's edge goes out byte by
+// byte.  No lane ever writes a byte it does not own, so neighbours never race.
+struct NoWin {};  // (WinGeo: decode_batch.h)
 template <bool WIN>
 using WinArg = std::conditional_t<WIN, WinGeo, NoWin>;
+struct __attribute__((packed, aligned(1))) PackedU32 {
+  uint32_t v;
+};
 // PITCH (the batched decode, whole planes): the chroma planes' rows are cpitch bytes
 // apart instead of packed.
-template <bool WIN = false, bool PITCH = false>
+template <bool WIN = false, bool PITCH = false, bool CROP = false>
 __device__ __forceinline__ void colour_block(const uint32_t (&px)[16], int bi, int bj, int nbx, int nby, int lane,
                                              bool live, const uint8_t *__restrict__ cr, const uint8_t *__restrict__ cb,
                                              uint8_t *__restrict__ rgb, int64_t rgb_stride,
-                                             const WinArg<WIN> &g = WinArg<WIN>{}, int wbi = 0, int64_t cpitch = 0) {
+                                             const WinArg<WIN> &g = WinArg<WIN>{}, int wbi = 0, int64_t cpitch = 0,
+                                             int crop_h = 0, int crop_w = 0) {
+  static_assert(!CROP || WIN, "the cropped store is the window form's");
   const int w = 4 * nbx, h = 4 * nby;
   // The packed pixels are opaque: otherwise the compiler forwards each truncated
   // pixel past its packing to the byte extracts below, and 64 live values instead
@@ -436,7 +443,25 @@ __device__ __forceinline__ void colour_block(const uint32_t (&px)[16], int bi, i
         }
       }
     }
-    if (live) {
+    if constexpr (CROP) {
+      const int row = 8 * bi + r8 - g.oy;
+      if (live && row >= 0 && row < crop_h) {
+        // byte k of the lane's 24 is byte c0 + k of the result's row: it is stored when
+        // lo <= k < hi (the pointer below is formed, never dereferenced, outside that)
+        const int c0 = 24 * bj - 3 * g.ox, lo = -c0, hi = 3 * crop_w - c0;
+        uint8_t *d = rgb + (int64_t)row * rgb_stride + c0;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+          if (4 * k >= lo && 4 * k + 4 <= hi) {
+            reinterpret_cast<PackedU32 *>(d + 4 * k)->v = o[k];
+          } else {
+#pragma unroll
+            for (int b = 0; b < 4; ++b)
+              if (4 * k + b >= lo && 4 * k + b < hi) d[4 * k + b] = (uint8_t)(o[k] >> (8 * b));
+          }
+        }
+      }
+    } else if (live) {
       int oy = 0, ox = 0;
       if constexpr (WIN) oy = g.oy, ox = g.ox;
       uint2 *d = reinterpret_cast<uint2 *>(rgb + (int64_t)(8 * bi + r8 - oy) * rgb_stride + (24 * bj - 3 * ox));
@@ -490,12 +515,15 @@ struct DecPlane {
 // 1 << RSH, rsh_arg is not read and the slot gather has no branch on it.  PITCH (the
 // batch): the chroma planes' rows are `ostride` (plane form, stored as dwords: a
 // multiple of 4, not of 8) or `cpitch` (RGB form, read) bytes apart.
-template <int TABLE, bool FAST, bool RGB, bool SLOTS, bool WIN, bool PITCH = false, int RSH = -1>
+// CROP (the batched region decode's luma launch): colour_block's cropped store into a
+// crop_h x crop_w x 3 result.
+template <int TABLE, bool FAST, bool RGB, bool SLOTS, bool WIN, bool PITCH = false, int RSH = -1, bool CROP = false>
 __device__ __forceinline__ void decode_tile(const DecPlane &p, int64_t t, uint2 *tile, int lane, int H, int W, int nbx,
                                             int64_t nblk, int64_t ostride, const uint8_t *__restrict__ cr,
                                             const uint8_t *__restrict__ cb, int rsh_arg, const WinArg<WIN> &wg,
-                                            int wbi, bool wfirst, int64_t cpitch = 0) {
+                                            int wbi, bool wfirst, int64_t cpitch = 0, int crop_h = 0, int crop_w = 0) {
   static_assert(!PITCH || (FAST && !WIN), "the pitched form holds whole planes of whole blocks");
+  static_assert(!CROP || (RGB && WIN), "the cropped store is the RGB window form's");
   const int rsh = RSH >= 0 ? RSH : rsh_arg;
   const int64_t ntiles = (nblk + 63) / 64;
   int16_t *win = reinterpret_cast<int16_t *>(tile);
@@ -549,7 +577,10 @@ __device__ __forceinline__ void decode_tile(const DecPlane &p, int64_t t, uint2 
   if constexpr (RGB || PITCH) {
     uint32_t px[16];
     idct_block_px<TABLE>(qv, px);
-    if constexpr (RGB && WIN) {
+    if constexpr (CROP) {
+      colour_block<true, false, true>(px, bi, bj, nbx, H / 8, lane, lane < nvb, cr, cb, p.out, ostride, wg, wbi, 0,
+                                      crop_h, crop_w);
+    } else if constexpr (RGB && WIN) {
       colour_block<true>(px, bi, bj, nbx, H / 8, lane, lane < nvb, cr, cb, p.out, ostride, wg, wbi);
     } else if constexpr (RGB) {
       colour_block<false, PITCH>(px, bi, bj, nbx, H / 8, lane, lane < nvb, cr, cb, p.out, ostride, NoWin{}, 0, cpitch);
@@ -670,6 +701,59 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HIC_DEC_WPE
   const uint8_t *cr = RGB ? ent->c[1].out : nullptr, *cb = RGB ? ent->c[2].out : nullptr;
   decode_tile<TABLE, true, RGB, SLOTS, false, true, RGB ? 0 : 1>(pl, t, s_tile[wv], lane, a.H, a.W, a.nbx, a.nblk,
                                                                  a.ostride, cr, cb, 0, NoWin{}, 0, false, a.cstride);
+}
+
+// The batched window form (hic_decode420_window_batch_u8, decode_batch.h): per wave the
+// decode_tile of k_rld_idct_indexed<TABLE, true, RGB, SLOTS, WIN>, the plane's pointers
+// AND its window geometry read from the batch's table by scalar loads.  With g =
+// blockIdx.x * 4 + wave and T = a.waves (uniform for the launch: the largest nrows * tpr
+// any image of the batch plans, twice that in the chroma launch): image g / T, and
+// within the image r = g % T enumerates (block row, k-th tile of the row) exactly as
+// the one-image window form does with the image's OWN geometry: Cb's waves follow Cr's
+// own nrows * tpr, a wave beyond its image's rows or its row's tiles returns.  The RGB
+// form stores cropped (colour_block's CROP) into the image's h x w x 3 result, rows of
+// a.ostride bytes; the plane form stores the chroma span into the image's chroma window
+// buffer, rows of a.ostride bytes, which the RGB form then reads through g.cpitch.
+struct DecWinBatchArgs {
+  const DecWinBatchEntry *tab;
+  uint32_t total, waves;  // n * T, T
+  int H, W, nbx;          // of the launch's planes
+  int crop_h, crop_w;     // RGB form: the result's rows and columns
+  int64_t nblk;
+  int64_t ostride;
+};
+template <int TABLE, bool RGB, bool SLOTS>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HIC_DEC_WPE))) void k_rld_idct_window_batch(
+    DecWinBatchArgs a) {
+  static_assert(!RGB || TABLE == 0, "the RGB form decodes luma planes");
+  __shared__ uint2 s_tile[4][64 * kRowI16 / 4];
+  const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint32_t g = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (uint32_t)wv);
+  if (g >= a.total) return;
+  const uint32_t img = g / a.waves;
+  int r = (int)(g - img * a.waves);
+  typedef const __attribute__((address_space(4))) DecWinBatchEntry centry;
+  centry *ent = (centry *)(uintptr_t)(a.tab + img);
+  const int gi = RGB ? 0 : 1;
+  const WinGeo wg{ent->g[gi].bi0, ent->g[gi].nrows, ent->g[gi].bj0, ent->g[gi].bj1, ent->g[gi].tpr,   ent->g[gi].oy,
+                  ent->g[gi].ox,  ent->g[gi].cy0,   ent->g[gi].cx0, ent->g[gi].ch,  ent->g[gi].cw,    ent->g[gi].cpitch,
+                  ent->g[gi].n_ac};
+  // every quantity here is wave-uniform (scalar), as in k_rld_idct_indexed's window form
+  const int nw = wg.nrows * wg.tpr;
+  const bool second = !RGB && r >= nw;  // Cb's waves follow Cr's
+  if (second) r -= nw;
+  if (r >= nw) return;
+  const int row = r / wg.tpr, wbi = wg.bi0 + row;
+  const int64_t rb = (int64_t)wbi * a.nbx;
+  const int64_t t = (rb + wg.bj0) / 64 + (r - row * wg.tpr);
+  if (t > (rb + wg.bj1 - 1) / 64) return;
+  const int ch = RGB ? 0 : (second ? 2 : 1);
+  const DecPlane pl{ent->c[ch].sym_len, ent->c[ch].sym_val, ent->c[ch].d_nsym, ent->c[ch].dc_diff,
+                    static_cast<const int64_t *>(ent->c[ch].index), ent->c[ch].out, ent->c[ch].d_status};
+  const uint8_t *cr = RGB ? ent->c[1].out : nullptr, *cb = RGB ? ent->c[2].out : nullptr;
+  decode_tile<TABLE, true, RGB, SLOTS, true, false, RGB ? 0 : 1, RGB>(pl, t, s_tile[wv], lane, a.H, a.W, a.nbx, a.nblk,
+                                                                      a.ostride, cr, cb, 0, wg, wbi, r == 0, 0,
+                                                                      a.crop_h, a.crop_w);
 }
 
 // Production forward kernel for aligned planes: up to three planes per launch
@@ -1354,6 +1438,24 @@ static int tiles_per_row(int nbx, int bi0, int nrows, int bj0, int bj1) {
   return m;
 }
 
+// The kernels' geometry of one window launch: the luma launch over the aligned window
+// (rgb) or the chroma launch over the chroma span, of a plane nbx blocks wide; cstride
+// the chroma pitch the RGB form reads through.
+static WinGeo window_geo(bool rgb, const hic_window &w, int nbx, int64_t cstride) {
+  WinGeo g{};
+  if (rgb) {
+    g.bi0 = (int)(w.Y0 / 8), g.nrows = (int)((w.Y1 - w.Y0) / 8), g.bj0 = (int)(w.X0 / 8), g.bj1 = (int)(w.X1 / 8);
+    g.oy = (int)w.Y0, g.ox = (int)w.X0;
+  } else {
+    g.bi0 = (int)(w.cy0 / 8), g.nrows = (int)(w.ch / 8), g.bj0 = (int)(w.cx0 / 8), g.bj1 = (int)((w.cx0 + w.cw) / 8);
+    g.oy = (int)w.cy0, g.ox = (int)w.cx0;
+  }
+  g.cy0 = (int)w.cy0, g.cx0 = (int)w.cx0, g.ch = (int)w.ch, g.cw = (int)w.cw, g.cpitch = (int)cstride;
+  g.tpr = tiles_per_row(nbx, g.bi0, g.nrows, g.bj0, g.bj1);
+  g.n_ac = (int64_t)g.nrows * (g.bj1 - g.bj0) * 63;
+  return g;
+}
+
 // d.H, d.W: the IMAGE's shape (the chroma pair's planes are H/2 x W/2); cstride: the
 // RGB form's chroma pitch.  Every check before any device call.
 static int launch_rld_idct_window(const DecLaunch &d, int kind, const hic_window *win, int64_t cstride, void *stream) {
@@ -1387,17 +1489,7 @@ static int launch_rld_idct_window(const DecLaunch &d, int kind, const hic_window
     if (d.records_per_tile != 1 && d.records_per_tile != 2) return arg_error("records_per_tile must be 1 or 2");
     if (nblk % (64 / d.records_per_tile)) return arg_error("the plane's blocks must form whole records");
   }
-  WinGeo g{};
-  if (d.rgb) {
-    g.bi0 = (int)(w.Y0 / 8), g.nrows = (int)((w.Y1 - w.Y0) / 8), g.bj0 = (int)(w.X0 / 8), g.bj1 = (int)(w.X1 / 8);
-    g.oy = (int)w.Y0, g.ox = (int)w.X0;
-  } else {
-    g.bi0 = (int)(w.cy0 / 8), g.nrows = (int)(w.ch / 8), g.bj0 = (int)(w.cx0 / 8), g.bj1 = (int)((w.cx0 + w.cw) / 8);
-    g.oy = (int)w.cy0, g.ox = (int)w.cx0;
-  }
-  g.cy0 = (int)w.cy0, g.cx0 = (int)w.cx0, g.ch = (int)w.ch, g.cw = (int)w.cw, g.cpitch = (int)cstride;
-  g.tpr = tiles_per_row(nbx, g.bi0, g.nrows, g.bj0, g.bj1);
-  g.n_ac = (int64_t)g.nrows * (g.bj1 - g.bj0) * 63;
+  const WinGeo g = window_geo(d.rgb, w, nbx, cstride);
   const int64_t waves = (int64_t)d.nplanes * g.nrows * g.tpr;
   const dim3 grid((unsigned)((waves + 3) / 4)), block(256);
   hipStream_t s = as_stream(stream);
@@ -1565,6 +1657,179 @@ extern "C" int hic_decode420_batch_u8(const void *h_table, const void *d_table, 
   if (slots) hipLaunchKernelGGL((k_rld_idct_batch<0, true, true>), dim3((unsigned)h.grid_y), block, 0, s, a);
   else hipLaunchKernelGGL((k_rld_idct_batch<0, true, false>), dim3((unsigned)h.grid_y), block, 0, s, a);
   return check_launch("k_rld_idct_batch<rgb>");
+}
+
+// ---- batched region decode: a window per image, n images of one shape, in two
+// launches (decode_batch.h, DESIGN.md section 5, "Batched region decode").
+// The largest aligned window and chroma span any origin can plan for an h x w request
+// (pipeline.region_capacity), and the most waves per image each launch can then need.
+struct WinCapacity {
+  int64_t wh, ww, ch, cw;
+  int64_t waves_y, waves_c;  // (waves_c: both chroma planes)
+};
+static WinCapacity window_capacity(int64_t H, int64_t W, int64_t h, int64_t w) {
+  auto up16 = [](int64_t v) { return (v + 15) / 16 * 16; };
+  WinCapacity c{};
+  c.wh = std::min(H, up16(h + 15)), c.ww = std::min(W, up16(w + 15));
+  c.ch = std::min(H / 2, c.wh / 2 + 16), c.cw = std::min(W / 2, c.ww / 2 + 16);
+  // a run of L blocks of a raster touches at most (L + 62) / 64 + 1 tiles
+  auto tpr = [](int64_t L, int64_t nblk) { return std::min((L + 62) / 64 + 1, (nblk + 63) / 64); };
+  c.waves_y = c.wh / 8 * tpr(c.ww / 8, (H / 8) * (W / 8));
+  c.waves_c = 2 * (c.ch / 8 * tpr(c.cw / 8, (H / 16) * (W / 16)));
+  return c;
+}
+
+// The header of (kind, n, image shape, window shape, strides) but for the waves per
+// image and the grids, which follow from the origins; nullptr = good, else what is wrong.
+static const char *dec_win_batch_header(int kind, int n, int64_t H, int64_t W, int64_t h, int64_t w,
+                                        int64_t out_row_stride, int64_t chroma_pitch, int64_t chroma_rows,
+                                        DecWinBatchHeader &o) {
+  DecBatchHeader whole;
+  // (kind, n and the image shape as the whole-image batch takes them)
+  if (const char *e = dec_batch_header(kind, n, H, W, 3 * W, W / 2, whole)) return e;
+  if (h < 1 || w < 1 || h > H || w > W) return "window shape (1 <= h <= H, 1 <= w <= W)";
+  if (out_row_stride < 3 * w || out_row_stride >= ((int64_t)1 << 31)) return "out_row_stride (>= 3 w, below 2^31)";
+  const WinCapacity cap = window_capacity(H, W, h, w);
+  // 8-byte chroma row stores, dword chroma loads; colour_block's row offsets are 32-bit
+  if (chroma_pitch < cap.cw || chroma_pitch % 8) return "chroma_pitch (>= the capacity's columns, a multiple of 8)";
+  if (chroma_rows < cap.ch) return "chroma_rows (>= the capacity's rows)";
+  if (chroma_rows >= ((int64_t)1 << 31) / chroma_pitch) return "chroma window buffer too large";
+  // (the kernel counts waves in 32 bits, unsigned)
+  if (n * std::max(cap.waves_y, cap.waves_c) + 3 > (int64_t)INT32_MAX) return "grid above INT32_MAX / 4 workgroups";
+  o = DecWinBatchHeader{};
+  o.magic = kDecWinBatchMagic;
+  o.kind = kind, o.n = n, o.H = H, o.W = W, o.h = h, o.w = w;
+  o.out_row_stride = out_row_stride, o.chroma_pitch = chroma_pitch, o.chroma_rows = chroma_rows;
+  o.nblk_y = whole.nblk_y, o.nblk_c = whole.nblk_c;
+  return nullptr;
+}
+
+static void dec_win_batch_grids(DecWinBatchHeader &o, int64_t waves_y, int64_t waves_c) {
+  o.waves_y = (int32_t)waves_y, o.waves_c = (int32_t)waves_c;
+  o.grid_y = (int32_t)((o.n * waves_y + 3) / 4), o.grid_c = (int32_t)((o.n * waves_c + 3) / 4);
+}
+
+extern "C" size_t hic_decode_window_batch_table_bytes(int n) {
+  if (n < 1 || n > HIC_DECODE_BATCH_MAX) return 0;
+  return sizeof(DecWinBatchHeader) + (size_t)n * sizeof(DecWinBatchEntry);
+}
+
+extern "C" int hic_decode_window_batch_table(int kind, int n, int64_t H, int64_t W, int64_t h, int64_t w,
+                                             const hic_decode_image *images, const int64_t *origins,
+                                             int64_t out_row_stride, int64_t chroma_pitch, int64_t chroma_rows,
+                                             void *h_table, size_t table_bytes) {
+  DecWinBatchHeader hd;
+  if (const char *e = dec_win_batch_header(kind, n, H, W, h, w, out_row_stride, chroma_pitch, chroma_rows, hd))
+    return arg_error(e);
+  if (!images || !origins || !h_table) return arg_error("null pointer");
+  if (table_bytes < hic_decode_window_batch_table_bytes(n))
+    return arg_error("table of %lld bytes, %lld needed", (long long)table_bytes,
+                     (long long)hic_decode_window_batch_table_bytes(n));
+  // every image checked and planned before a byte is written
+  const bool slots = kind == HIC_STREAM_SLOTS;
+  const WinCapacity cap = window_capacity(H, W, h, w);
+  std::vector<DecWinBatchEntry> ents((size_t)n);
+  int64_t waves_y = 1, waves_c = 2;
+  for (int i = 0; i < n; ++i) {
+    for (int k = 0; k < 3; ++k) {
+      const hic_decode_plane &p = images[i].c[k];
+      if (!p.sym_len || !p.sym_val || !p.d_nsym || !p.dc_diff || !p.d_index || !p.out || !p.d_status)
+        return arg_error("image %d channel %d: null pointer", i, k);
+      // the gathers read the symbols as uint4s
+      if (!aligned(p.sym_len, 16) || !aligned(p.sym_val, 16))
+        return arg_error("image %d channel %d: %s arrays must be 16-byte aligned", i, k, slots ? "slot" : "symbol");
+      // 8-byte chroma row stores and dword chroma loads; the pixels are stored at any alignment
+      if (k > 0 && !aligned(p.out, 8))
+        return arg_error("image %d channel %d: the chroma window buffer must be 8-byte aligned", i, k);
+      if (!aligned(p.d_nsym, 8) || !aligned(p.d_status, 8) || !aligned(p.dc_diff, 4) ||
+          !aligned(p.d_index, slots ? 4 : 8))
+        return arg_error("image %d channel %d: count / status / DC / index alignment", i, k);
+    }
+    const int64_t y0 = origins[2 * i], x0 = origins[2 * i + 1];
+    hic_window win;
+    if (y0 < 0 || x0 < 0 || y0 > H - h || x0 > W - w || window_plan(H, W, y0, x0, h, w, &win))
+      return arg_error("image %d: window (%lld, %lld, %lld, %lld) outside the image", i, (long long)y0, (long long)x0,
+                       (long long)h, (long long)w);
+    if (win.Y1 - win.Y0 > cap.wh || win.X1 - win.X0 > cap.ww || win.ch > chroma_rows || win.cw > chroma_pitch)
+      return arg_error("image %d: the window's plan exceeds the capacity", i);
+    DecWinBatchEntry e{};
+    for (int k = 0; k < 3; ++k) {
+      const hic_decode_plane &p = images[i].c[k];
+      e.c[k] = DecBatchPlane{p.sym_len, p.sym_val, p.d_nsym, p.dc_diff, p.d_index, p.out, p.d_status};
+    }
+    e.g[0] = window_geo(true, win, (int)(W / 8), chroma_pitch);
+    e.g[0].oy = (int)y0, e.g[0].ox = (int)x0;  // the store crops: out's first pixel is the request's
+    e.g[1] = window_geo(false, win, (int)(W / 16), chroma_pitch);
+    e.y0 = (int32_t)y0, e.x0 = (int32_t)x0;
+    waves_y = std::max(waves_y, (int64_t)e.g[0].nrows * e.g[0].tpr);
+    waves_c = std::max(waves_c, 2 * (int64_t)e.g[1].nrows * e.g[1].tpr);
+    ents[(size_t)i] = e;
+  }
+  if (waves_y > cap.waves_y || waves_c > cap.waves_c) return arg_error("internal: waves per image above the capacity's");
+  // no two outputs of the batch may overlap (pixels, chroma window buffers, status words)
+  {
+    struct Range {
+      uintptr_t at, bytes;
+      int image, chan, status;
+    };
+    std::vector<Range> r;
+    r.reserve((size_t)6 * n);
+    for (int i = 0; i < n; ++i)
+      for (int k = 0; k < 3; ++k) {
+        const hic_decode_plane &p = images[i].c[k];
+        const int64_t bytes = k == 0 ? (h - 1) * out_row_stride + 3 * w : chroma_rows * chroma_pitch;
+        r.push_back(Range{reinterpret_cast<uintptr_t>(p.out), (uintptr_t)bytes, i, k, 0});
+        r.push_back(Range{reinterpret_cast<uintptr_t>(p.d_status), 8, i, k, 1});
+      }
+    std::sort(r.begin(), r.end(), [](const Range &x, const Range &y) { return x.at < y.at; });
+    const char *what[2] = {"output", "status word"};
+    for (size_t i = 0; i + 1 < r.size(); ++i)
+      if (r[i].at + r[i].bytes > r[i + 1].at)
+        return arg_error("image %d channel %d: its %s overlaps the %s of image %d channel %d", r[i + 1].image,
+                         r[i + 1].chan, what[r[i + 1].status], what[r[i].status], r[i].image, r[i].chan);
+  }
+  dec_win_batch_grids(hd, waves_y, waves_c);
+  memcpy(h_table, &hd, sizeof hd);
+  memcpy(static_cast<char *>(h_table) + sizeof hd, ents.data(), (size_t)n * sizeof(DecWinBatchEntry));
+  return HIC_OK;
+}
+
+extern "C" int hic_decode420_window_batch_u8(const void *h_table, const void *d_table, void *stream) {
+  if (!h_table || !d_table) return arg_error("null pointer");
+  if (!aligned(d_table, 16)) return arg_error("d_table must be 16-byte aligned");
+  DecWinBatchHeader h;
+  memcpy(&h, h_table, sizeof h);
+  if (h.magic != kDecWinBatchMagic) return arg_error("not a window decode batch table (magic)");
+  DecWinBatchHeader want;
+  if (const char *e = dec_win_batch_header(h.kind, h.n, h.H, h.W, h.h, h.w, h.out_row_stride, h.chroma_pitch,
+                                           h.chroma_rows, want))
+    return arg_error(e);
+  // the waves per image follow from the origins: any value up to the capacity's is a
+  // table's (a wave checks itself against its own image's geometry), the rest must match
+  const WinCapacity cap = window_capacity(h.H, h.W, h.h, h.w);
+  if (h.waves_y < 1 || h.waves_y > cap.waves_y || h.waves_c < 2 || h.waves_c % 2 || h.waves_c > cap.waves_c)
+    return arg_error("damaged window decode batch table header");
+  dec_win_batch_grids(want, h.waves_y, h.waves_c);
+  if (memcmp(&want, &h, sizeof want)) return arg_error("damaged window decode batch table header");
+  DecWinBatchArgs a{};
+  a.tab = reinterpret_cast<const DecWinBatchEntry *>(static_cast<const char *>(d_table) + sizeof h);
+  const bool slots = h.kind == HIC_STREAM_SLOTS;
+  hipStream_t s = as_stream(stream);
+  const dim3 block(256);
+  // every image's Cr and Cb spans into its chroma window buffers ...
+  a.total = (uint32_t)h.n * (uint32_t)h.waves_c, a.waves = (uint32_t)h.waves_c;
+  a.H = (int)(h.H / 2), a.W = (int)(h.W / 2), a.nbx = (int)(h.W / 16), a.nblk = h.nblk_c;
+  a.ostride = h.chroma_pitch;
+  if (slots) hipLaunchKernelGGL((k_rld_idct_window_batch<1, false, true>), dim3((unsigned)h.grid_c), block, 0, s, a);
+  else hipLaunchKernelGGL((k_rld_idct_window_batch<1, false, false>), dim3((unsigned)h.grid_c), block, 0, s, a);
+  if (int e = check_launch("k_rld_idct_window_batch<chroma>")) return e;
+  // ... then every image's Y tiles of its aligned window straight to RGB, cropped
+  a.total = (uint32_t)h.n * (uint32_t)h.waves_y, a.waves = (uint32_t)h.waves_y;
+  a.H = (int)h.H, a.W = (int)h.W, a.nbx = (int)(h.W / 8), a.nblk = h.nblk_y;
+  a.crop_h = (int)h.h, a.crop_w = (int)h.w, a.ostride = h.out_row_stride;
+  if (slots) hipLaunchKernelGGL((k_rld_idct_window_batch<0, true, true>), dim3((unsigned)h.grid_y), block, 0, s, a);
+  else hipLaunchKernelGGL((k_rld_idct_window_batch<0, true, false>), dim3((unsigned)h.grid_y), block, 0, s, a);
+  return check_launch("k_rld_idct_window_batch<rgb>");
 }
 
 extern "C" int hic_dct2_f64(const double *in, int64_t nblk, double *out, void *stream) {

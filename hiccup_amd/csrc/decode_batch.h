@@ -42,4 +42,45 @@ struct DecBatchHeader {
 };
 static_assert(sizeof(DecBatchHeader) == 128, "table header size");
 
+// ---- the batched region decode (hic_decode_window_batch_table,
+// hic_decode420_window_batch_u8): a window of one size h x w per image, each image at
+// its own origin, cropped into one dense (n, h, w, 3) result by the same two launches.
+// A table format of its own: besides the pointers an entry holds the geometry of its
+// image's two window launches, which the waves read by scalar loads as they read the
+// pointers.
+constexpr uint64_t kDecWinBatchMagic = 0x3157434544434948ull;  // "HICDECW1"
+
+// The geometry of one window launch over one plane (dct.hip, colour_block's and
+// k_rld_idct_indexed's window forms).
+struct WinGeo {
+  int bi0, nrows, bj0, bj1;  // the launch plane's block rows [bi0, bi0 + nrows), columns [bj0, bj1)
+  int tpr;                   // waves per block row (the most tiles a row's columns touch)
+  int oy, ox;                // the plane coordinates of out's first sample
+  int cy0, cx0, ch, cw;      // RGB form: the chroma planes' span
+  int cpitch;
+  int64_t n_ac;              // *d_status of a good launch: 63 per block of the window
+};
+static_assert(sizeof(WinGeo) == 56, "window geometry size");
+
+struct DecWinBatchEntry {
+  DecBatchPlane c[3];  // Y (out: the image's h x w x 3 pixels), Cr, Cb (out: its chroma window buffer)
+  WinGeo g[2];         // the luma launch (oy, ox = the request's y0, x0: the store crops), the chroma launch
+  int32_t y0, x0;      // the request's origin
+  int64_t pad[28];     // 512 bytes, a power of two
+};
+static_assert(sizeof(DecWinBatchEntry) == 512, "window table entry size");
+
+struct DecWinBatchHeader {
+  uint64_t magic;
+  int32_t kind, n;
+  int64_t H, W, h, w;                  // the images' shape; the windows' shape
+  int64_t out_row_stride;              // bytes between the pixel rows of one image's result
+  int64_t chroma_pitch, chroma_rows;   // of every chroma window buffer (rows of chroma_pitch bytes)
+  int32_t waves_y, waves_c;            // T of each launch: waves per image, the largest any image plans
+  int32_t grid_y, grid_c;              // workgroups of the luma / the chroma launch
+  int64_t nblk_y, nblk_c;              // blocks of the Y plane / of one chroma plane
+  int64_t pad[3];
+};
+static_assert(sizeof(DecWinBatchHeader) == 128, "window table header size");
+
 }  // namespace hic

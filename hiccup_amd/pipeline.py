@@ -794,7 +794,9 @@ class BatchDecoder:
                      index[k].data_ptr()]
         return slots, addr
 
-    def _table(self, sources, stream):
+    def _resolve(self, sources):
+        """The sources' (kind, addresses) when they differ from the previous call's, else
+        None (self._key then holds them)."""
         # The same BatchEncoder, or the same Encoder objects, as the previous call: an
         # Encoder's buffers are allocated once, so the addresses are the same too, and
         # the 15 n data_ptr() reads (several us per image on the host, more than the
@@ -804,7 +806,7 @@ class BatchDecoder:
         objs = (sources,) if whole else tuple(sources)
         if self._objs is not None and self._objs[0] == whole and len(objs) == len(self._objs[1]) and all(
                 a is b for a, b in zip(objs, self._objs[1])):
-            return
+            return None
         self._objs = None
         sources = objs[0].encoders if whole else list(objs)
         if len(sources) != self.n:
@@ -816,7 +818,15 @@ class BatchDecoder:
         remember = (whole, objs) if all(isinstance(x, Encoder) for x in sources) else None
         if key == self._key:
             self._objs = remember
+            return None
+        return key, remember
+
+    def _table(self, sources, stream):
+        new = self._resolve(sources)
+        if new is None:
             return
+        key, remember = new
+        kinds, addrs = (key[0],), key[1]
         n, H, W = self.n, self.H, self.W
         if kinds[0] and not batch_decode_eligible(n, H, W, slots=True):
             raise ValueError("slot-layout sources need planes of whole records")
@@ -994,6 +1004,128 @@ class RegionDecoder:
         st = self.status.cpu().tolist()
         if st != self.expected_status():
             raise ValueError("region decode status %r, expected %r" % (st, self.expected_status()))
+
+
+# ------------------------------------------------------------------ batched region decode
+def batch_region_eligible(n, H, W, h, w, slots=False):
+    """Whether BatchRegionDecoder takes an h x w window from each of n images of H x W
+    (hic_decode_window_batch_table's limits): what batch_decode_eligible asks of n, H, W
+    (and of the planes' records for slot-layout sources), 1 <= h <= H, 1 <= w <= W, and
+    a chroma window buffer (region_capacity) below 2^31 bytes."""
+    if not batch_decode_eligible(n, H, W, slots=slots):
+        return False
+    if not (1 <= h <= H and 1 <= w <= W) or 3 * w >= 2**31:
+        return False
+    (wh, ww), (ch, cw) = region_capacity(H, W, h, w)
+    if ch >= 2**31 // cw:
+        return False
+    # the most waves per image either launch can need (a run of L blocks touches at most
+    # (L + 62) // 64 + 1 tiles), in 32-bit wave counts
+    ty = wh // 8 * min((ww // 8 + 62) // 64 + 1, -(-_nblk(H, W) // 64))
+    tc = 2 * (ch // 8 * min((cw // 8 + 62) // 64 + 1, -(-_nblk(H // 2, W // 2) // 64)))
+    return n * max(ty, tc) + 3 <= 2**31 - 1
+
+
+class BatchRegionDecoder:
+    """RegionDecoder.decode of one window per image, n images of one shape, in TWO
+    launches (hic_decode420_window_batch_u8): every image's chroma span into its chroma
+    window buffer, then every image's Y tiles of its aligned covering window straight to
+    RGB, the store cropped to the request -- no aligned scratch window and no copies to
+    form one tensor.  The windows share their size h x w; each image has its own origin.
+    out (n, h, w, 3): out[i] equals Decoder(H, W).decode(index=...)[y0:y0+h, x0:x0+w] of
+    image i bit for bit.  cr / cb (n, rows, pitch): the chroma window buffers, each of
+    region_capacity's size; status (n, 3).  out=: a caller's (n, h, w, 3) uint8 device
+    view to decode into (dense pixels, any row and image strides, any alignment)."""
+
+    def __init__(self, n, H, W, h, w, out=None):
+        if not batch_region_eligible(n, H, W, h, w):
+            raise ValueError("a region decode batch needs 1 <= n <= %d images with H and W multiples of 16 and a "
+                             "window of 1..H x 1..W" % DECODE_BATCH_MAX)
+        device.require_gpu()
+        self.n, self.H, self.W, self.h, self.w = n, H, W, h, w
+        if out is None:
+            out = device.empty((n, h, w, 3), torch.uint8)
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.uint8
+                  and tuple(out.shape) == (n, h, w, 3) and out.stride(3) == 1 and out.stride(2) == 3
+                  and out.stride(1) >= 3 * w and (n == 1 or out.stride(0) >= (h - 1) * out.stride(1) + 3 * w)):
+            raise ValueError("out must be a (%d, %d, %d, 3) uint8 device tensor of dense pixels" % (n, h, w))
+        self.out = out
+        _, (ch, cw) = region_capacity(H, W, h, w)
+        self.cr = device.empty((n, ch, cw), torch.uint8)
+        self.cb = device.empty((n, ch, cw), torch.uint8)
+        self.status = device.zeros((n, 3), torch.int64)
+        self.origins = None
+        nbytes = _lib.load().hic_decode_window_batch_table_bytes(n)
+        # the table's host copy is pinned, so its upload is one queued DMA; _sent guards
+        # the host copy against being rewritten while that DMA still reads it
+        self._h_table = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+        self._d_table = device.empty((nbytes,), torch.uint8)
+        self._sent = None
+        self._key = self._objs = self._images = None
+
+    _source = BatchDecoder._source
+    _resolve = BatchDecoder._resolve
+
+    def decode(self, sources, origins, stream=None):
+        """sources as BatchDecoder.decode takes them (a BatchEncoder, n Encoders, or n
+        tuples (sym_len, sym_val, counts, dc, index)), all of one kind; origins: n (y0,
+        x0) pairs.  The sources' 15 n addresses are read again only when the sources are
+        not the previous call's objects; every call plans the n windows afresh
+        (hic_decode_window_batch_table, microseconds on the host), uploads the table
+        (the call's one host-to-device copy) and makes the two launches.  Nothing is
+        read back.  Returns self.out."""
+        new = self._resolve(sources)
+        n, H, W, h, w = self.n, self.H, self.W, self.h, self.w
+        if new is not None:
+            (slots, addrs), remember = new
+            if slots and not batch_region_eligible(n, H, W, h, w, slots=True):
+                raise ValueError("slot-layout sources need planes of whole records")
+            images = (_lib.DecodeImage * n)()
+            outs = (self.cr, self.cb)
+            for i, a in enumerate(addrs):
+                for c in range(3):
+                    o = self.out.data_ptr() + i * self.out.stride(0) if c == 0 else outs[c - 1][i].data_ptr()
+                    images[i].c[c] = _lib.DecodePlane(*a[5 * c:5 * c + 5], o, self.status.data_ptr() + 8 * (3 * i + c))
+            self._key, self._objs, self._images = (slots, addrs), remember, images
+        origins = [(int(y0), int(x0)) for y0, x0 in origins]
+        if len(origins) != n:
+            raise ValueError("%d origins for a batch of %d" % (len(origins), n))
+        flat = (ctypes.c_int64 * (2 * n))(*(v for o in origins for v in o))
+        if self._sent is not None:
+            self._sent.synchronize()
+        _lib.call("hic_decode_window_batch_table", _lib.STREAM_SLOTS if self._key[0] else _lib.STREAM_INDEXED, n, H, W,
+                  h, w, self._images, flat, self.out.stride(1), self.cr.stride(1), self.cr.shape[1],
+                  self._h_table.data_ptr(), self._h_table.numel())
+        with device.on_stream(stream):
+            self._d_table.copy_(self._h_table, non_blocking=True)
+            self._sent = torch.cuda.Event()
+            self._sent.record()
+        _lib.call("hic_decode420_window_batch_u8", self._h_table.data_ptr(), device.ptr(self._d_table),
+                  device.stream_ptr(stream))
+        self.origins = origins
+        return self.out
+
+    def plans(self):
+        """The last decode's window_plan per image."""
+        return [window_plan(self.H, self.W, y0, x0, self.h, self.w) for y0, x0 in self.origins]
+
+    def expected_status(self):
+        """What a good decode leaves in self.status: per image, 63 per block of each
+        launch's window (RegionDecoder.expected_status)."""
+        rows = []
+        for p in self.plans():
+            c = (p.ch // 8) * (p.cw // 8) * 63
+            rows.append([((p.Y1 - p.Y0) // 8) * ((p.X1 - p.X0) // 8) * 63, c, c])
+        return rows
+
+    def check_status(self):
+        """Raise if a channel's symbol count of any image was a failed encode's (status
+        -1; one read, syncs).  A window does not see the whole stream: its completeness
+        is stream_index's status, or the encoder's."""
+        st, want = self.status.cpu().tolist(), self.expected_status()
+        for i, (got, exp) in enumerate(zip(st, want)):
+            if got != exp:
+                raise ValueError("image %d: region decode status %r, expected %r" % (i, got, exp))
 
 
 def stream_index(sym_len, sym_val, counts, dc, H, W, stream=None):

@@ -685,6 +685,37 @@ size_t hic_decode_batch_table_bytes(int n);
 int hic_decode_batch_table(int kind, int n, int64_t H, int64_t W, int64_t rgb_stride, int64_t chroma_stride,
                            const hic_decode_image *images, void *h_table, size_t table_bytes);
 int hic_decode420_batch_u8(const void *h_table, const void *d_table, void *stream);
+/* Batched region decode: a window of one size h x w from each of n images of one shape
+ *  (H, W multiples of 16; all of one stream kind), image i's window at its own origin
+ *  (origins[2 i], origins[2 i + 1]) = (y0, x0).  Image i's result is h rows of
+ *  out_row_stride bytes (>= 3 w; any alignment) at images[i].c[0].out and equals rows
+ *  [y0, y0 + h) x columns [x0, x0 + w) of the whole-image decode bit for bit.  TWO
+ *  launches for the whole batch: every image's Cr and Cb chroma spans (hic_window_plan's
+ *  cy0, cx0, ch, cw of its own window) into its chroma window buffers images[i].c[1].out
+ *  / c[2].out -- chroma_rows rows of chroma_pitch bytes each, 8-byte aligned,
+ *  chroma_pitch a multiple of 8 and both at least the largest span any origin can plan
+ *  (for the aligned window up to min(H, ceil16(h + 15)) x min(W, ceil16(w + 15)): half
+ *  of it plus 16, clipped to the chroma plane) -- then every image's Y tiles of its
+ *  aligned covering window straight to RGB, the store cropped to the request.  No
+ *  aligned scratch window, no second pass.
+ *  hic_decode_window_batch_table plans every image as hic_window_plan does and fills a
+ *    host blob of hic_decode_window_batch_table_bytes(n) bytes (0 unless 1 <= n <=
+ *    HIC_DECODE_BATCH_MAX); needs no GPU.  Everything is checked before a byte is
+ *    written; HIC_ERR_ARG for what hic_decode_batch_table refuses of kind, n, shape and
+ *    the streams' pointers, a window shape outside 1..H x 1..W, a window outside its
+ *    image (the message names the image), out_row_stride < 3 w, a bad chroma_pitch /
+ *    chroma_rows, a short table_bytes, and any two outputs of the batch (pixels, chroma
+ *    window buffers, status words) that overlap.  The blob has a format of its own
+ *    (decode_batch.h): hic_decode420_batch_u8 refuses it, and the reverse.
+ *  hic_decode420_window_batch_u8: the caller uploads the blob (16-byte aligned) and
+ *    passes both copies; the header is re-derived and compared, then the two launches
+ *    on one stream.  *d_status of every (image, channel): -1 when *d_nsym < 1 (then that
+ *    launch writes nothing of that image), else 63 per block of that launch's window. */
+size_t hic_decode_window_batch_table_bytes(int n);
+int hic_decode_window_batch_table(int kind, int n, int64_t H, int64_t W, int64_t h, int64_t w,
+                                  const hic_decode_image *images, const int64_t *origins, int64_t out_row_stride,
+                                  int64_t chroma_pitch, int64_t chroma_rows, void *h_table, size_t table_bytes);
+int hic_decode420_window_batch_u8(const void *h_table, const void *d_table, void *stream);
 /* One tile shard's slice of the channel stream (the sharded decode of
  * codec.jpeg_decode, codec.py:397-425): d_stitch is the shard's device record from
  * hic_rle_stitch {carry zeros, closes the stream, has previous DC, previous DC}.
