@@ -50,7 +50,7 @@ __device__ __forceinline__ uint32_t pack4(uint32_t b0, uint32_t b1, uint32_t b2,
 }
 
 // Packed 16-bit pairs (cr | cb << 16) and the YCrCb -> RGB dot products of the
-// decode colour kernels (color.hip k_ycrcb420_rgb_walk, dct.hip k_rld_idct_rgb_indexed).
+// decode colour kernels (color.hip k_ycrcb420_rgb_walk, decode.hip colour_block).
 typedef unsigned short u16x2c __attribute__((ext_vector_type(2)));
 typedef short s16x2c __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ uint32_t pk_add_u16(uint32_t a, uint32_t b) {

@@ -1,6 +1,6 @@
 // dct_core.h -- the bit-exact 8x8 DCT-II / DCT-III + quantizer building blocks
-// shared by the transform kernels (dct.hip) and the fused plane encoder
-// (encode.hip).  See dct.hip for the design notes and reference citations.
+// shared by the transform kernels (dct.hip), the fused plane encoder (encode.hip) and
+// the fused tile decoders (decode.hip).  See dct.hip for the design notes and citations.
 #pragma once
 #include "hic_common.h"
 
@@ -565,6 +565,84 @@ __host__ __device__ __forceinline__ int dc_quant(int X) {
   const int a = 8 * X + T;                        // 2 (4X) + T
   const int q = (a >= 0 ? a : a - (2 * T - 1)) / (2 * T);  // floor(a / 2T)
   return (a == q * 2 * T && (q & 1)) ? q - 1 : q;  // exact tie: to even
+}
+
+// One block's dequantize + DCT-III down to packed pixels: the epilogue of the inverse
+// transform kernel (dct.hip) and of the fused tile decoders (decode.hip).
+__device__ __forceinline__ double sreg_f64(double k) {  // opaque wave-uniform constant
+  asm volatile("" : "+s"(k));
+  return k;
+}
+__device__ __forceinline__ double vreg_f64(double k) {
+  asm volatile("" : "+v"(k));
+  return k;
+}
+__device__ __forceinline__ double fma_scale_add(double y, double k_s, double c_v) {  // fl(y * k + c), one rounding
+  double d;
+  asm("v_fma_f64 %0, %1, %2, %3" : "=v"(d) : "v"(y), "s"(k_s), "v"(c_v));
+  return d;
+}
+
+// Dequantize (q * T, exact in int32), the 2-D DCT-III in pocketfft's float64
+// operation order, /256 + 128, truncate, wrap, and store the 8x8 pixels of the
+// block at (y0, x0) of the H x W plane (FAST: whole block inside, 8-byte rows).
+template <int TABLE>
+__device__ __forceinline__ void idct_block_px(const int (&q)[64], uint32_t (&px)[16]) {
+  // dequantize (q * T, exact in int32) and row pass
+  double a[8][8];
+#pragma unroll
+  for (int u = 0; u < 8; ++u) {
+    int c[8];
+#pragma unroll
+    for (int v = 0; v < 8; ++v) c[v] = q[u * 8 + v] * QT[TABLE][u * 8 + v];
+    idct8<int>(c, a[u]);
+  }
+  // column pass, /256 (exact) + 128, truncate toward zero, wrap mod 256.  The
+  // constants live in registers (2^-8 an SGPR pair, 128 a VGPR pair) for a
+  // three-address v_fma_f64: LLVM's v_fmac_f64 form overwrote its accumulator,
+  // so it re-materialised 128.0 (two v_mov_b32) before each of the 64 fmas
+  const double k2m8 = sreg_f64(0x1p-8), k128 = vreg_f64(128.0);
+  // row r: bytes v = 0..3 in px[2r], 4..7 in px[2r+1].  A truncated value's low
+  // byte is the wrapped pixel; bytes are packed by byte permutes, a pair of columns
+  // per v_perm and two pairs per dword (3 instructions per 4 pixels)
+  uint32_t even[8];  // row r's pixel of the even column of the pair being packed
+#pragma unroll
+  for (int v = 0; v < 8; ++v) {
+    double xc[8], yv[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) xc[u] = a[u][v];
+    idct8<double>(xc, yv);
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+      const double p = fma_scale_add(yv[r], k2m8, k128);  // == fl(y/256 + 128): y*2^-8 exact
+      const uint32_t b = (uint32_t)__double2int_rz(p);
+      if (!(v & 1)) {
+        even[r] = b;
+      } else {
+        const uint32_t pair = __builtin_amdgcn_perm(b, even[r], 0x0C0C0400u);  // even.b0 | b.b0 << 8
+        uint32_t &d = px[2 * r + (v >> 2)];
+        d = (v & 2) ? __builtin_amdgcn_perm(pair, d, 0x05040100u) : pair;
+      }
+    }
+  }
+}
+template <int TABLE, bool FAST>
+__device__ __forceinline__ void idct_block_store(const int (&q)[64], int H, int W, int y0, int x0,
+                                                 uint8_t *__restrict__ out, int64_t ostride) {
+  uint32_t px[16];
+  idct_block_px<TABLE>(q, px);
+  if (FAST) {
+    uint8_t *o = out + (int64_t)y0 * ostride + x0;  // one 64-bit multiply; rows step by the uniform stride
+#pragma unroll
+    for (int r = 0; r < 8; ++r) *reinterpret_cast<uint2 *>(o + r * ostride) = make_uint2(px[2 * r], px[2 * r + 1]);
+  } else {
+#pragma unroll
+    for (int r = 0; r < 8; ++r)
+#pragma unroll
+      for (int v = 0; v < 8; ++v)
+        if (y0 + r < H && x0 + v < W)
+          out[(int64_t)(y0 + r) * ostride + x0 + v] = (uint8_t)(px[2 * r + (v >> 2)] >> (8 * (v & 3)));
+  }
 }
 
 }  // namespace

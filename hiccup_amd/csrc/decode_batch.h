@@ -1,6 +1,6 @@
 // decode_batch.h -- the per-batch table of the batched decode (hic_decode_batch_table,
 // hic_decode420_batch_u8): N images of one shape, each decoded as the one-image fused
-// tile decoders decode it (k_rld_idct_indexed, dct.hip), by two launches for the whole
+// tile decoders decode it (k_rld_idct_indexed, decode.hip), by two launches for the whole
 // batch: every image's Cr and Cb tiles, then every image's Y tiles straight to RGB.
 // The 21 per-image pointers (per channel the symbols or slots, the count, the DC
 // differences, the index, the output and the status word) do not fit by-value kernel
@@ -50,7 +50,7 @@ static_assert(sizeof(DecBatchHeader) == 128, "table header size");
 // pointers.
 constexpr uint64_t kDecWinBatchMagic = 0x3157434544434948ull;  // "HICDECW1"
 
-// The geometry of one window launch over one plane (dct.hip, colour_block's and
+// The geometry of one window launch over one plane (decode.hip, colour_block's and
 // k_rld_idct_indexed's window forms).
 struct WinGeo {
   int bi0, nrows, bj0, bj1;  // the launch plane's block rows [bi0, bi0 + nrows), columns [bj0, bj1)

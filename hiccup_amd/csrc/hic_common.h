@@ -47,6 +47,12 @@ inline int hip_status(hipError_t e, const char *what) {
 
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
+inline bool aligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+// a plane the transform and decode kernels reach: one lane per 8x8 block, int32 block / element indices
+inline bool plane_dims_ok(int64_t H, int64_t W) {
+  return H > 0 && W > 0 && H < (1 << 20) && W < (1 << 20) && ((H + 7) / 8) * ((W + 7) / 8) < (1LL << 31) / 256;
+}
+
 constexpr int kWave = 64;
 
 // Round n up to a multiple of a.

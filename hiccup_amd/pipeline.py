@@ -615,6 +615,19 @@ class BatchEncoder:
                                         + [hic.TupP(h, w), hic.TupP(hc, wc)]) for i, one in enumerate(packed)]
 
 
+def stream_addresses(sym_len, sym_val, counts, dc, index, i, k):
+    """Channel k's (the i-th of CHANNELS) five stream addresses as the indexed entry
+    points and a DecodePlane take them: symbol (or slot) lengths, values, its word of
+    the device count tensor (3,), the DC differences, the index."""
+    return (sym_len[k].data_ptr(), sym_val[k].data_ptr(), counts.data_ptr() + 8 * i, dc[k].data_ptr(),
+            index[k].data_ptr())
+
+
+def _two(a, b):
+    """Host array of two addresses (Cr's, Cb's): an argument of the *_pair entry points."""
+    return (ctypes.c_void_p * 2)(a, b)
+
+
 class Decoder:
     """Inverse chain: symbols -> zig-zag blocks -> pixels -> RGB (2h x 2w x 3)."""
 
@@ -655,37 +668,34 @@ class Decoder:
         kind = "slots" if slots else "indexed"
         if slots:
             sym_len, sym_val = index.slot_len, index.slot_val
-
-        def src(i, k):
-            """Channel k's stream for an indexed entry point: (symbol lengths, values, device
-            count, DC differences), the index, and () or (records per tile,)."""
-            return ((sym_len[k].data_ptr(), sym_val[k].data_ptr(), counts.data_ptr() + 8 * i, dc[k].data_ptr()),
-                    index[k].data_ptr(), (index.rpt[k],) if slots else ())
+        # per channel, an indexed entry point's stream arguments: the five addresses
+        # (the index last), then () or (records per tile,)
+        addr, rpt = {}, {}
+        if index is not None:
+            for i, k in enumerate(CHANNELS):
+                addr[k] = stream_addresses(sym_len, sym_val, counts, dc, index, i, k)
+                rpt[k] = (index.rpt[k],) if slots else ()
 
         def status(i):
             return self.status.data_ptr() + 8 * i
 
         def decode_plane(i, k):
             """Channel k's symbols to its pixel plane, one kernel."""
-            sym, ix, rpt = src(i, k)
-            _lib.call("hic_rle_decode_idct_u8_" + kind, *sym, ix, *rpt, *self.shapes[k], TABLES[k],
+            _lib.call("hic_rle_decode_idct_u8_" + kind, *addr[k], *rpt[k], *self.shapes[k], TABLES[k],
                       self.pix[k].data_ptr(), self.pix[k].stride(0), status(i), s)
 
         cr, cb = self.pix["cr"].data_ptr(), self.pix["cb"].data_ptr()
         if index is not None and not keep_blocks and not planes and self.H % 8 == 0 and self.W % 8 == 0:
             # Cr and Cb in one launch (one tail), then Y straight to RGB
             if self.chroma_pair:
-                two = lambda a, b: (ctypes.c_void_p * 2)(a, b)  # noqa: E731
-                (sym_r, ix_r, rpt), (sym_b, ix_b, _) = src(1, "cr"), src(2, "cb")
-                _lib.call("hic_rle_decode_idct_u8_%s_pair" % kind, *map(two, sym_r, sym_b), two(ix_r, ix_b), *rpt,
-                          *self.shapes["cr"], TABLES["cr"], two(cr, cb), self.pix["cr"].stride(0),
-                          two(status(1), status(2)), s)
+                _lib.call("hic_rle_decode_idct_u8_%s_pair" % kind, *map(_two, addr["cr"], addr["cb"]), *rpt["cr"],
+                          *self.shapes["cr"], TABLES["cr"], _two(cr, cb), self.pix["cr"].stride(0),
+                          _two(status(1), status(2)), s)
             else:
                 decode_plane(1, "cr")
                 decode_plane(2, "cb")
-            sym, ix, rpt = src(0, "lum")
-            _lib.call("hic_rle_decode_idct_rgb_" + kind, *sym, ix, *rpt, self.H, self.W, cr, cb, self.rgb.data_ptr(),
-                      self.rgb.stride(0), status(0), s)
+            _lib.call("hic_rle_decode_idct_rgb_" + kind, *addr["lum"], *rpt["lum"], self.H, self.W, cr, cb,
+                      self.rgb.data_ptr(), self.rgb.stride(0), status(0), s)
             return self.rgb
         for i, k in enumerate(CHANNELS):
             h, w = self.shapes[k]
@@ -696,8 +706,8 @@ class Decoder:
             if index is not None:
                 # (the block-level forms take the block count, then the records per tile,
                 # before the index)
-                sym, ix, rpt = src(i, k)
-                _lib.call("hic_rle_decode_i16_" + kind, *sym, n, *rpt, ix, self.blocks[k].data_ptr(), status(i), s)
+                _lib.call("hic_rle_decode_i16_" + kind, *addr[k][:4], n, *rpt[k], addr[k][4], self.blocks[k].data_ptr(),
+                          status(i), s)
             else:
                 nsym = int(counts[i])
                 need = lib.hic_rld_workspace_bytes(nsym, n)
@@ -741,25 +751,13 @@ def batch_decode_eligible(n, H, W, slots=False):
     return 4 * -(-n * ty // 4) <= 2**32 - 1 and 4 * -(-n * tc // 4) <= 2**32 - 1
 
 
-class BatchDecoder:
-    """Decoder.decode(index=...) of n images of one shape in TWO launches
-    (hic_decode420_batch_u8) instead of two per image: every image's Cr and Cb tiles,
-    then every image's Y tiles straight to RGB.  A 512 x 512 image is 8 + 16
-    workgroups of the tile decoder, and a run of such launches is bound by launch
-    latency.  Per image the results are bit for bit those of Decoder(H, W).decode:
-    rgb (n, H, W, 3), cr / cb (n, H/2, W/2), status (n, 3)."""
+class _DecodeSources:
+    """The sources of a decode batch of self.n images of self.H x self.W (BatchDecoder,
+    BatchRegionDecoder): their kind and stream addresses, read again only when the
+    sources change (self._key, self._objs), and the DecodeImage array the table
+    builders take."""
 
-    def __init__(self, n, H, W):
-        if not batch_decode_eligible(n, H, W):
-            raise ValueError("a decode batch needs 1 <= n <= %d images with H and W multiples of 16"
-                             % DECODE_BATCH_MAX)
-        device.require_gpu()
-        self.n, self.H, self.W = n, H, W
-        self.rgb = device.empty((n, H, W, 3), torch.uint8)
-        self.cr = device.empty((n, H // 2, W // 2), torch.uint8)
-        self.cb = device.empty((n, H // 2, W // 2), torch.uint8)
-        self.status = device.zeros((n, 3), torch.int64)
-        self._key = self._h_table = self._d_table = self._objs = None
+    _key = _objs = None
 
     def _source(self, i, src):
         """Source i as (kind, the 15 stream addresses: per channel symbols / slots, values,
@@ -790,8 +788,7 @@ class BatchDecoder:
             want = 4 * (nblk[c] * SLOT_RPT[k] // 64) if slots else 3 * -(-nblk[c] // 64)
             if index[k].numel() != want or (slots and sym_len[k].numel() != nblk[c] * 63):
                 raise ValueError("source %d channel %s: the index is not a %d x %d image's" % (i, k, self.H, self.W))
-            addr += [sym_len[k].data_ptr(), sym_val[k].data_ptr(), counts.data_ptr() + 8 * c, dc[k].data_ptr(),
-                     index[k].data_ptr()]
+            addr += stream_addresses(sym_len, sym_val, counts, dc, index, c, k)
         return slots, addr
 
     def _resolve(self, sources):
@@ -821,6 +818,37 @@ class BatchDecoder:
             return None
         return key, remember
 
+    def _decode_images(self, addrs, outs):
+        """The DecodeImage array of the resolved addresses: image i's Y, Cr, Cb planes
+        decode into outs[0][i], outs[1][i], outs[2][i] and report in self.status[i]."""
+        images = (_lib.DecodeImage * self.n)()
+        for i, a in enumerate(addrs):
+            for c in range(3):
+                images[i].c[c] = _lib.DecodePlane(*a[5 * c:5 * c + 5], outs[c][i].data_ptr(),
+                                                  self.status.data_ptr() + 8 * (3 * i + c))
+        return images
+
+
+class BatchDecoder(_DecodeSources):
+    """Decoder.decode(index=...) of n images of one shape in TWO launches
+    (hic_decode420_batch_u8) instead of two per image: every image's Cr and Cb tiles,
+    then every image's Y tiles straight to RGB.  A 512 x 512 image is 8 + 16
+    workgroups of the tile decoder, and a run of such launches is bound by launch
+    latency.  Per image the results are bit for bit those of Decoder(H, W).decode:
+    rgb (n, H, W, 3), cr / cb (n, H/2, W/2), status (n, 3)."""
+
+    def __init__(self, n, H, W):
+        if not batch_decode_eligible(n, H, W):
+            raise ValueError("a decode batch needs 1 <= n <= %d images with H and W multiples of 16"
+                             % DECODE_BATCH_MAX)
+        device.require_gpu()
+        self.n, self.H, self.W = n, H, W
+        self.rgb = device.empty((n, H, W, 3), torch.uint8)
+        self.cr = device.empty((n, H // 2, W // 2), torch.uint8)
+        self.cb = device.empty((n, H // 2, W // 2), torch.uint8)
+        self.status = device.zeros((n, 3), torch.int64)
+        self._h_table = self._d_table = None
+
     def _table(self, sources, stream):
         new = self._resolve(sources)
         if new is None:
@@ -830,12 +858,7 @@ class BatchDecoder:
         n, H, W = self.n, self.H, self.W
         if kinds[0] and not batch_decode_eligible(n, H, W, slots=True):
             raise ValueError("slot-layout sources need planes of whole records")
-        images = (_lib.DecodeImage * n)()
-        outs = (self.rgb, self.cr, self.cb)
-        for i, a in enumerate(addrs):
-            for c in range(3):
-                images[i].c[c] = _lib.DecodePlane(*a[5 * c:5 * c + 5], outs[c][i].data_ptr(),
-                                                  self.status.data_ptr() + 8 * (3 * i + c))
+        images = self._decode_images(addrs, (self.rgb, self.cr, self.cb))
         nbytes = _lib.load().hic_decode_batch_table_bytes(n)
         h_table = ctypes.create_string_buffer(nbytes)
         _lib.call("hic_decode_batch_table", _lib.STREAM_SLOTS if kinds[0] else _lib.STREAM_INDEXED, n, H, W, 3 * W,
@@ -919,6 +942,14 @@ def window_tiles(plan, W, chroma=False):
             for t in range((bi * nbx + bj0) // 64, (bi * nbx + bj1 - 1) // 64 + 1)]
 
 
+def window_status(plan):
+    """The three status words a good window decode of `plan` leaves (Y, Cr, Cb): 63 per
+    block of each launch's window, the aligned window for Y and the chroma span for
+    Cr and Cb."""
+    c = (plan.ch // 8) * (plan.cw // 8) * 63
+    return [((plan.Y1 - plan.Y0) // 8) * ((plan.X1 - plan.X0) // 8) * 63, c, c]
+
+
 def region_capacity(H, W, max_h, max_w):
     """((rows, columns) of the largest aligned window, (rows, columns) of the largest
     chroma span) any request (h, w) <= (max_h, max_w) of an H x W image can plan: an
@@ -961,20 +992,15 @@ class RegionDecoder:
         kind = _lib.STREAM_SLOTS if slots else _lib.STREAM_INDEXED
         if slots:
             sym_len, sym_val = index.slot_len, index.slot_val
-
-        def src(i, k):
-            return (sym_len[k].data_ptr(), sym_val[k].data_ptr(), counts.data_ptr() + 8 * i, dc[k].data_ptr(),
-                    index[k].data_ptr())
-
-        two = lambda a, b: (ctypes.c_void_p * 2)(a, b)  # noqa: E731
+        y, cr, cb = (stream_addresses(sym_len, sym_val, counts, dc, index, i, k) for i, k in enumerate(CHANNELS))
         st = [self.status.data_ptr() + 8 * i for i in range(3)]
         win = plan.c_struct()
         # the windows are packed: pitch = the window's own width
-        _lib.call("hic_rle_decode_idct_u8_window_pair", kind, *map(two, src(1, "cr"), src(2, "cb")),
+        _lib.call("hic_rle_decode_idct_u8_window_pair", kind, *map(_two, cr, cb),
                   index.rpt["cr"] if slots else 0, self.H, self.W, ctypes.byref(win),
-                  two(self.cr.data_ptr(), self.cb.data_ptr()), plan.cw, two(st[1], st[2]), s)
+                  _two(self.cr.data_ptr(), self.cb.data_ptr()), plan.cw, _two(st[1], st[2]), s)
         Ww = plan.X1 - plan.X0
-        _lib.call("hic_rle_decode_idct_rgb_window", kind, *src(0, "lum"), index.rpt["lum"] if slots else 0, self.H,
+        _lib.call("hic_rle_decode_idct_rgb_window", kind, *y, index.rpt["lum"] if slots else 0, self.H,
                   self.W, ctypes.byref(win), self.cr.data_ptr(), self.cb.data_ptr(), plan.cw, self.rgb.data_ptr(),
                   3 * Ww, st[0], s)
         self.plan = plan
@@ -992,10 +1018,8 @@ class RegionDecoder:
         return tuple(b[:p.ch * p.cw].view(p.ch, p.cw) for b in (self.cr, self.cb))
 
     def expected_status(self):
-        """What a good decode leaves in self.status: 63 per block of each launch's window."""
-        p = self.plan
-        c = (p.ch // 8) * (p.cw // 8) * 63
-        return [((p.Y1 - p.Y0) // 8) * ((p.X1 - p.X0) // 8) * 63, c, c]
+        """What a good decode leaves in self.status (window_status of the last plan)."""
+        return window_status(self.plan)
 
     def check_status(self):
         """Raise if a channel's symbol count was a failed encode's (status -1; syncs).
@@ -1026,7 +1050,7 @@ def batch_region_eligible(n, H, W, h, w, slots=False):
     return n * max(ty, tc) + 3 <= 2**31 - 1
 
 
-class BatchRegionDecoder:
+class BatchRegionDecoder(_DecodeSources):
     """RegionDecoder.decode of one window per image, n images of one shape, in TWO
     launches (hic_decode420_window_batch_u8): every image's chroma span into its chroma
     window buffer, then every image's Y tiles of its aligned covering window straight to
@@ -1061,10 +1085,7 @@ class BatchRegionDecoder:
         self._h_table = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
         self._d_table = device.empty((nbytes,), torch.uint8)
         self._sent = None
-        self._key = self._objs = self._images = None
-
-    _source = BatchDecoder._source
-    _resolve = BatchDecoder._resolve
+        self._images = None
 
     def decode(self, sources, origins, stream=None):
         """sources as BatchDecoder.decode takes them (a BatchEncoder, n Encoders, or n
@@ -1080,12 +1101,7 @@ class BatchRegionDecoder:
             (slots, addrs), remember = new
             if slots and not batch_region_eligible(n, H, W, h, w, slots=True):
                 raise ValueError("slot-layout sources need planes of whole records")
-            images = (_lib.DecodeImage * n)()
-            outs = (self.cr, self.cb)
-            for i, a in enumerate(addrs):
-                for c in range(3):
-                    o = self.out.data_ptr() + i * self.out.stride(0) if c == 0 else outs[c - 1][i].data_ptr()
-                    images[i].c[c] = _lib.DecodePlane(*a[5 * c:5 * c + 5], o, self.status.data_ptr() + 8 * (3 * i + c))
+            images = self._decode_images(addrs, (self.out, self.cr, self.cb))
             self._key, self._objs, self._images = (slots, addrs), remember, images
         origins = [(int(y0), int(x0)) for y0, x0 in origins]
         if len(origins) != n:
@@ -1111,12 +1127,8 @@ class BatchRegionDecoder:
 
     def expected_status(self):
         """What a good decode leaves in self.status: per image, 63 per block of each
-        launch's window (RegionDecoder.expected_status)."""
-        rows = []
-        for p in self.plans():
-            c = (p.ch // 8) * (p.cw // 8) * 63
-            rows.append([((p.Y1 - p.Y0) // 8) * ((p.X1 - p.X0) // 8) * 63, c, c])
-        return rows
+        launch's window (window_status)."""
+        return [window_status(p) for p in self.plans()]
 
     def check_status(self):
         """Raise if a channel's symbol count of any image was a failed encode's (status

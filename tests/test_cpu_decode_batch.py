@@ -128,6 +128,13 @@ def test_table_refuses_bad_planes_in_any_image():
                      images=_bad(_images(5), i, k, sym_val=base + GAP + 2))
             _refused(who + ": out must be 8-byte aligned", IDX, 5, 48, 80,
                      images=_bad(_images(5), i, k, out=base + 5 * GAP + 4))
+            _refused(who + ": count / status / DC / index alignment", IDX, 5, 48, 80,
+                     images=_bad(_images(5), i, k, d_nsym=base + 2 * GAP + 4))
+            _refused(who + ": count / status / DC / index alignment", IDX, 5, 48, 80,
+                     images=_bad(_images(5), i, k, d_index=base + 4 * GAP + 4))
+            # (the slot layout's record index is int32: 4 bytes are enough)
+            rc, _ = _build(SLOTS, 5, 16, 512, images=_bad(_images(5), i, k, d_index=base + 4 * GAP + 4))
+            assert rc == _lib.HIC_OK, _lib.last_error()
 
 
 def test_table_refuses_overlapping_outputs():

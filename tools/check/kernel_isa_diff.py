@@ -4,13 +4,14 @@ bodies of every kernel whose name contains SUBSTR in two device assembly listing
 
     hipcc --offload-arch=gfx950 <the Makefile's flags> --cuda-device-only -S file.hip -o listing.s
 
-of the same source file at two commits.  Kernels are matched by name and leading
-template arguments, a kernel without template arguments on either side by its name
-alone (a new trailing template parameter renames every instantiation; --new-suffix
-picks the instantiations of the new listing that stand for the old ones, e.g. 'Lb0E'
-for a new bool parameter that is false).  Symbol names are
-normalised before comparing, so only instructions, labels and directives inside
-the bodies count.  Also prints each kernel's VGPRs, SGPRs, scratch and kernarg
+of the same source file at two commits, or of the file a kernel moved out of and the
+one it moved into.  Kernels are matched by name and leading template arguments, a
+kernel without template arguments on either side by its name alone (a new trailing
+template parameter renames every instantiation; --new-suffix picks the instantiations
+of the new listing that stand for the old ones, e.g. 'Lb0E' for a new bool parameter
+that is false).  Symbol names and the file-wide numbering of local labels are
+normalised before comparing, so only instructions, labels and directives inside the
+bodies count.  Also prints each kernel's VGPRs, SGPRs, scratch and kernarg
 bytes, and its instruction count.  Exit status 1 when a body differs or a kernel has
 no counterpart."""
 import argparse
@@ -30,8 +31,17 @@ def bodies(path, sub):
             if line.startswith("\t.section") or line.startswith(".Lfunc_end"):
                 cur = None
             else:
-                out[cur].append(re.sub(r"_Z\w*%s\w*" % re.escape(sub), "K", line))
+                out[cur].append(local_labels(re.sub(r"_Z\w*%s\w*" % re.escape(sub), "K", line)))
     return out
+
+
+def local_labels(line):
+    """Block and jump-table labels carry the function's ordinal in its file (.LBB36_3,
+    'Header=BB36_92' in a comment): drop it, and the padding before a label's comment
+    that its length shifts, so a kernel that moved to another file (or past other
+    functions) still compares."""
+    line = re.sub(r"(?<!\w)(\.L)?(BB|JTI)\d+_(\d+)", r"\1\2_\3", line)
+    return re.sub(r"^(\.L\w+:)\s+;", r"\1 ;", line)
 
 
 def resources(path, sub):
