@@ -164,6 +164,8 @@ SIGNATURES = {
     "hic_slots_fill_batch": (_int, [_int, _vp, _int, _vp, _int, _vp]),
     "hic_encode420_batch_u8": (_int, [_int, _vp, _int, _vp, _vp, _vp]),
     "hic_huffman_decode_batch": (_int, [_int, _vp, _vp]),
+    "hic_huffman_decode_table_workspace_bytes": (_sz, [_int, _vp]),
+    "hic_huffman_decode_table": (_int, [_int, _vp, _vp, _sz, _vp]),
     "hic_huffman_from_codes": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "hic_huffman_pack": (_int, [_vp, _int, _i64, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp, _i64, _vp, _vp,
                                 _vp]),

@@ -345,12 +345,15 @@ def _decoding_tree(data):
     return flat if flat is not None else huffman_decode(data)
 
 
-def _huffman_streams_device(payloads, trees):
+def _huffman_streams_device(payloads, trees, table=None):
     """_huffman_stream_device of every (payload, tree) -- codec.jpeg_decode's nine
-    huffman_data_decode calls (codec.py:372-388) -- in ONE hic_huffman_decode_batch:
-    the bits go up in one copy, the streams share each phase's host wait.  Errors as
-    the reference's sequential decode raises them: the first failing stream in
-    payload order."""
+    huffman_data_decode calls (codec.py:372-388), or the 9 n of a batch -- in ONE
+    library call: the bits go up in one copy, the streams share each phase's host
+    wait.  table: through hic_huffman_decode_table (huffman.decode_table_jobs: one
+    launch per phase over all streams) or, False, hic_huffman_decode_batch (every
+    phase once per stream); None asks huffman.decode_table_default.  Errors as the
+    reference's sequential decode raises them: the first failing stream in payload
+    order."""
     n = len(payloads)
     lib = _lib.load()
     res, errs, jobs_at = [None] * n, [None] * n, []
@@ -371,7 +374,23 @@ def _huffman_streams_device(payloads, trees):
         offs.append(tot)
         tot += words
         jobs_at.append((i, nbits, tree.decode_args()))
-    if jobs_at:
+    if table is None:
+        table = huffman.decode_table_default(len(jobs_at), sum(nb for _, nb, _ in jobs_at))
+    if jobs_at and table:
+        outs, jobs, st = huffman.decode_table_jobs([body for body, _ in bufs], [nb for _, nb, _ in jobs_at],
+                                                   [a for _, _, a in jobs_at])
+        if st != _lib.HIC_OK and all(j.status == _lib.HIC_OK for j in jobs):
+            _lib.check(st, "hic_huffman_decode_table")  # refused before anything ran
+        for k, (i, _, (_, _, h_vals, _, _)) in enumerate(jobs_at):
+            j = jobs[k]
+            if j.status == _lib.HIC_ERR_ARG:
+                # the reference's reduce steps into None: huffman.py:155-161
+                errs[i] = AttributeError("'NoneType' object has no attribute 'is_leaf'")
+            elif j.status != _lib.HIC_OK:
+                errs[i] = MemoryError("hic_huffman_decode_table: stream %d decoded %d symbols" % (i, j.count))
+            else:
+                res[i] = (outs[k], int(j.count), h_vals is not None)
+    elif jobs_at:
         dbits = device.to_device_parts([body for body, _ in bufs], offs, tot)
         jobs = (_lib.HuffDecodeJob * len(jobs_at))()
         keep = []

@@ -392,6 +392,74 @@ def _decode_flat(child, nnodes, h_vals, nleaves, minlen, bits_dev, nbits, out=No
     return out, int(count.value)
 
 
+DECODE_TABLE_MAX = 65535  # streams per hic_huffman_decode_table call (the grid's y)
+
+
+def decode_table_default(m, total_bits):
+    """Whether codec._huffman_streams_device decodes m streams of total_bits coded
+    bits in all through hic_huffman_decode_table (one launch per phase over a table
+    of the streams) rather than hic_huffman_decode_batch (every phase once per
+    stream).  The rule is True only for shapes where the table leg was measured at or
+    below the parent's loop (tools/micro/huffman_decode_table_ab.py).  That A/B has
+    not been run on an MI355X yet (DESIGN.md "Round 20"), so every shape keeps the
+    loop until it has; table=True on _huffman_streams_device, or
+    huffman.decode_streams, takes the table form meanwhile."""
+    return False  # (m <= DECODE_TABLE_MAX is the most the rule may ever accept)
+
+
+def decode_table_jobs(bodies, nbits, args, stream=None):
+    """hic_huffman_decode_table over m streams: bodies[i] the packed MSB-first bytes
+    of stream i (uint8, at least ceil(nbits[i] / 8) of them), args[i] its tree as
+    decode_args() gives it.  One upload of all bits (device.to_device_parts), one
+    int32 output buffer cut at per-stream offsets, one workspace, one library call.
+    Returns (outs, jobs, rc): outs[i] stream i's view of the output buffer (its
+    capacity nbits[i] // the shortest code, at least 1), jobs the call's
+    _lib.HuffDecodeJob array with every count and status, rc the call's status."""
+    lib = _lib.load()
+    m = len(bodies)
+    offs, tot, oo, caps, cap = [], 0, [], [], 0
+    for nb, a in zip(nbits, args):
+        offs.append(tot)
+        tot += -(-max(int(nb), 1) // 32) * 4
+        ml = a[4]() if callable(a[4]) else a[4]
+        oo.append(cap)
+        caps.append(max(int(nb) // ml, 1))
+        cap += -(-caps[-1] // 64) * 64  # every stream's output 256-byte aligned, as a tensor of its own is
+    with device.on_stream(stream):
+        dbits = device.to_device_parts([np.asarray(b, dtype=np.uint8)[:-(-int(nb) // 8)] for b, nb in zip(bodies, nbits)],
+                                       offs, tot)
+        out = device.empty((cap,), torch.int32)
+        jobs = (_lib.HuffDecodeJob * m)()
+        for k, (nb, (child, nnodes, h_vals, nleaves, _)) in enumerate(zip(nbits, args)):
+            jobs[k] = _lib.HuffDecodeJob(dbits.data_ptr() + offs[k], int(nb), child.ctypes.data, nnodes,
+                                         h_vals.ctypes.data if h_vals is not None else None, nleaves,
+                                         out.data_ptr() + 4 * oo[k], caps[k], None, 0, 0)
+        nbytes = lib.hic_huffman_decode_table_workspace_bytes(m, jobs)
+        ws = device.empty(((max(int(nbytes), 8) + 7) // 8,), torch.int64)  # (nothing in it is read before it is written)
+        rc = lib.hic_huffman_decode_table(m, jobs, device.ptr(ws), ws.numel() * 8, device.stream_ptr(stream))
+    return [out[o:o + c] for o, c in zip(oo, caps)], jobs, rc
+
+
+def decode_streams(payloads, trees, stream=None):
+    """decode_data of m packed streams in one hic_huffman_decode_table call: payloads[i]
+    = (packed uint8 array, nbits), trees[i] a HuffmanTree (not a one-leaf one) or
+    FlatCodes.  Returns [(int32 device tensor, count)]; a tree whose leaves are not all
+    int32 gives leaf indices, as decode_device does.  The first stream in order that
+    walks into a missing child raises AttributeError, as the reference's walk does."""
+    if not payloads:
+        return []
+    args = [t.decode_args() for t in trees]
+    outs, jobs, rc = decode_table_jobs([p for p, _ in payloads], [int(n) for _, n in payloads], args, stream)
+    if rc != _lib.HIC_OK and all(j.status == _lib.HIC_OK for j in jobs):
+        _lib.check(rc, "hic_huffman_decode_table")  # refused before anything ran
+    for i, j in enumerate(jobs):
+        if j.status == _lib.HIC_ERR_ARG:
+            raise AttributeError("'NoneType' object has no attribute 'is_leaf'")
+        if j.status != _lib.HIC_OK:
+            raise MemoryError("hic_huffman_decode_table: stream %d decoded %d symbols" % (i, j.count))
+    return [(o, int(j.count)) for o, j in zip(outs, jobs)]
+
+
 class CodeBook(_Packer):
     """The codes of the reference's tree over keys in first-appearance order with
     their counts, built in native code (hic_huffman_build: HuffmanTree._construct's

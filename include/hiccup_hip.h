@@ -795,6 +795,26 @@ typedef struct {
   int32_t status; /* out */
 } hic_huffman_decode_job;
 int hic_huffman_decode_batch(int n, hic_huffman_decode_job *jobs, void *stream);
+/* hic_huffman_decode_table: hic_huffman_decode_batch's results for m jobs (a batch
+ *    of n images' 9 n streams) in a fixed number of launches: the jobs go into a
+ *    table in device memory and every phase (the lookup tables, built on the GPU
+ *    from the uploaded trees; the first count; each resynchronisation round; the
+ *    sums, the scan, the output) is ONE launch over the whole table.  Every job is
+ *    checked as hic_huffman_decode_batch checks it before anything is queued
+ *    (HIC_ERR_ARG, nothing run: a bad tree, a null pointer, a misaligned d_bits, m
+ *    outside 0..65535, a null, misaligned (16 bytes) or short workspace).  Per job
+ *    count, status and d_out, and the returned first non-OK status, are exactly
+ *    hic_huffman_decode_batch's.  A job's own `workspace` is ignored: `workspace`
+ *    (>= hic_huffman_decode_table_workspace_bytes(m, jobs) bytes, which reads the
+ *    jobs' nbits, nnodes and nleaves; 0 for arguments the call refuses) serves all
+ *    of them and the library allocates nothing on the device.  All trees go up in
+ *    one copy from a staging buffer the call owns, the table in one more; the
+ *    host waits once per kRoundsPerSync rounds and once at the end.  Jobs with
+ *    nbits == 0 are skipped (count 0); m == 0 or only such jobs: HIC_OK, no device
+ *    work.  Synchronises the stream. */
+size_t hic_huffman_decode_table_workspace_bytes(int m, const hic_huffman_decode_job *jobs);
+int hic_huffman_decode_table(int m, hic_huffman_decode_job *jobs, void *workspace, size_t workspace_bytes,
+                             void *stream);
 
 /* ---- Huffman trees, host side (native, no device work; hufftree.hip).
  *  hic_huffman_build: HuffmanTree._construct (huffman.py:60-79) over n >= 1 leaves
